@@ -29,7 +29,15 @@ must then equal N; more ranks than visible GPUs is refused (exit 2).
 
 The JSON line is kept under 4 KB; the verbose record (every step's reader
 profile, every CLI run's diagnostics, notes) goes to --detail (default: a
-file in the temp directory, named on stderr).  Also in the line:
+file in the temp directory, named on stderr).
+
+A plain run does only what the headline needs: it sets up (panel, device
+table, reads, files), warms up, times the K steps and prints the line.
+--dump-outputs DIR then also writes what the last timed step computed, the
+all-reduced counts and the totals, as DIR/counts.npy and DIR/totals.npy
+(float64; the reads are seeded, so two builds given the same arguments can be
+compared output for output).  Everything else is measured and checked with
+--full only, and is null in a plain run's line:
   roofline      the counting kernel on HBM-resident reads (1 B
                 per base + 8 B per read) / its HIP-event-timed duration, against
                 8 TB/s HBM3E; traffic from a committed rocprofv3 PMC summary
@@ -197,21 +205,64 @@ def md5(path):
     return h.hexdigest()
 
 
-def write_fastq_from_device(d_seq, n, L, path, threads=8, first=0):
+def digits_total(m):
+    """Decimal digits of the numbers 0 .. m-1 together (0 has one)."""
+    t, d, lo = 0, 1, 0
+    while lo < m:
+        hi = 10 ** d
+        t += d * (min(m, hi) - lo)
+        lo, d = hi, d + 1
+    return t
+
+
+def write_fastq_from_device(d_seq, n, L, path, threads=8, first=0, step=500_000):
     """The first n HBM-resident reads of d_seq as 4-line FASTQ (@r<first+i>,
-    qualities 'I'); records are built by `threads` threads
-    (vafc_synth.fastq_bytes_np, the bytes of vafc_synth.fastq_bytes) and
-    written in order."""
+    qualities 'I'); records are built `step` reads at a time by `threads`
+    threads (vafc_synth.fastq_bytes_np, the bytes of vafc_synth.fastq_bytes).
+    A record is 2 L + 7 bytes and the digits of its read number, so every
+    piece's place in the file is known beforehand and each thread writes its
+    own pieces there (the file's pages are filled in parallel too).  The
+    calling thread copies the pieces' reads from the device, one after another,
+    into a small pool of pinned buffers that the threads hand back."""
+    import queue
+    import torch
     import vafc_synth as S
-    step = 500_000
+    threads = max(1, threads)
+    step = max(1, min(step, n))
 
-    def piece(a):
-        b = min(n, a + step)
-        return S.fastq_bytes_np(d_seq[a * L:b * L].cpu().numpy().reshape(b - a, L), first + a)
+    def at(i):   # the byte at which record i starts
+        return i * (2 * L + 7) + digits_total(first + i) - digits_total(first)
 
-    with open(path, "wb") as f, ThreadPoolExecutor(max(1, threads)) as ex:
-        for blob in ex.map(piece, range(0, n, step)):
-            f.write(blob)
+    pool = torch.empty((threads + 2, step * L), dtype=torch.uint8, pin_memory=d_seq.is_cuda)
+    free = queue.Queue()
+    for i in range(pool.shape[0]):
+        free.put(i)
+    fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+    try:
+        os.ftruncate(fd, at(n))
+
+        def piece(a, b, i):
+            try:
+                blob = memoryview(S.fastq_bytes_np(pool[i, :(b - a) * L].numpy().reshape(b - a, L), first + a))
+            finally:
+                free.put(i)
+            if len(blob) != at(b) - at(a):
+                raise RuntimeError("FASTQ piece %d: %d bytes, expected %d" % (a, len(blob), at(b) - at(a)))
+            done = 0
+            while done < len(blob):
+                done += os.pwrite(fd, blob[done:], at(a) + done)
+
+        with ThreadPoolExecutor(threads) as ex:
+            jobs = []
+            for a in range(0, n, step):
+                b = min(n, a + step)
+                i = free.get()
+                pool[i, :(b - a) * L].copy_(d_seq[a * L:b * L])   # returns with the bytes on the host
+                jobs.append(ex.submit(piece, a, b, i))
+            for j in jobs:
+                j.result()
+    finally:
+        os.close(fd)
 
 
 def scratch_dir(need_bytes, fallback):
@@ -624,6 +675,17 @@ def headline_leg(kmap, fqs, steps, warmup, rank, world, dist, cpu_group, dev, n_
     return e2e, final
 
 
+def dump_outputs(d, counts, totals):
+    """--dump-outputs: what the last timed step handed its caller, as float64
+    .npy files in directory d (every value is an integer below 2^53, so the
+    conversion is exact).  counts.npy: the uint32 counts, counts[2i] the ref and
+    counts[2i+1] the alt count of pattern i (all ranks' counts, all-reduced);
+    totals.npy: the k-mer tally, then (e2e) the sequences and bases read."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "counts.npy"), np.asarray(counts, dtype=np.uint32).astype(np.float64))
+    np.save(os.path.join(d, "totals.npy"), np.asarray(totals, dtype=np.float64))
+
+
 CONFIGS = {
     # name: (k, reads per file of this rank's stream, read seeds of the files, panel)
     "c2": (21, 100_000_000, None, "grch38"),
@@ -639,6 +701,14 @@ def assemble_line(a):
     parity booleans last."""
     e2e, cli, cpu = a.get("e2e"), a.get("cli"), a.get("cpu")
     headline = e2e is not None
+    roofline = None           # a plain e2e run does not run the kernel on HBM-resident reads (--full does)
+    if a.get("k_ms") is not None:
+        roofline = {"bound": "hbm", "achieved": round(a["achieved"], 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(a["achieved"] / HBM_PEAK_GBS, 4), "traffic": a["traffic"],
+                    "kernel": "vc_count_reads_kernel", "kernel_ms": round(a["k_ms"], 4),
+                    "kernel_launches": a["k_steps"], "kernel_value": round(a["k_value"], 1),
+                    "alg_bytes_per_launch": a["alg_bytes"], "alg_bytes_rule": "SURVEY.md 8(d): 1 B/base + 8 B/read",
+                    "limiter": a["limiter"]}
     line = {
         "metric": "Mbases/sec (+ k-mers/sec) on %d bp FASTQ, k=%d" % (a["L"], a["k"]),
         "value": e2e["value"] if headline else round(a["k_value"], 1),
@@ -660,12 +730,7 @@ def assemble_line(a):
                    "read_len": a["L"], "k": a["k"], "patterns": a["n_pat"], "files": a["n_files"],
                    "parallelism": a["parallelism"]},
         "kmers_per_sec": e2e["kmers_per_sec"] if headline else round(a["k_kmer_rate"], 1),
-        "roofline": {"bound": "hbm", "achieved": round(a["achieved"], 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(a["achieved"] / HBM_PEAK_GBS, 4), "traffic": a["traffic"],
-                     "kernel": "vc_count_reads_kernel", "kernel_ms": round(a["k_ms"], 4),
-                     "kernel_launches": a["k_steps"], "kernel_value": round(a["k_value"], 1),
-                     "alg_bytes_per_launch": a["alg_bytes"], "alg_bytes_rule": "SURVEY.md 8(d): 1 B/base + 8 B/read",
-                     "limiter": a["limiter"]},
+        "roofline": roofline,
         "cpu_baseline": cpu,
         "vs_cpu_baseline": round(e2e["value"] / cpu["value"], 1) if cpu and headline and e2e["value"] else None,
         "e2e": e2e,
@@ -700,7 +765,18 @@ def main():
     ap.add_argument("--no-e2e", action="store_true",
                     help="no FASTQ files: value = the kernel on HBM-resident reads (profiling runs)")
     ap.add_argument("--detail", default=None, help="where the verbose record goes (JSON)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the kernel roofline on "
+                         "HBM-resident reads, the CPU baseline and the parity sample against the reference, the "
+                         "full-size self-consistency check and the drop-in CLI leg (--no-cpu, --no-parity and "
+                         "--no-cli take legs away again)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float64): counts.npy, the interleaved (ref, alt) counts of every pattern, and "
+                         "totals.npy, the k-mer tally (e2e: then the sequences and bases read)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu = args.no_parity = args.no_cli = True
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         sys.exit(spawn_ranks(sys.argv[1:], args.gpus))
@@ -802,36 +878,42 @@ def main():
     torch.cuda.synchronize()
     log("rank %d: %d reads x %d bp generated in HBM in %.2fs" % (rank, R, L, time.time() - t0))
 
-    # ---- the counting kernel on HBM-resident reads (roofline)
-    counts = torch.zeros(2 * n_pat, dtype=torch.int32, device=dev)
-    tally = torch.zeros(1, dtype=torch.int64, device=dev)
-    k_steps, k_warm = (args.kernel_steps, 2) if headline else (args.steps, args.warmup)
-    k_elapsed, kernel_ms = kernel_leg(kmap, d_seq, d_offs, d_lens, R, L, k_steps, k_warm, world, dist, counts, tally)
+    # ---- the counting kernel on HBM-resident reads (roofline): the timed path
+    # of the kernel configs (c4, --no-e2e); beside the e2e headline only with --full
     reads_total = R
     if world > 1:
         n = torch.tensor([R], dtype=torch.int64, device=dev)
         dist.all_reduce(n)
         reads_total = int(n.item())
-    k_value = reads_total * L * k_steps / k_elapsed / 1e6
-    k_kmer_rate = int(tally.item()) * k_steps / k_elapsed
-    k_ms = float(np.mean(kernel_ms))
-    # algorithmic bytes as SURVEY.md section 8(d) defines them: 1 B per base +
-    # 8 B per read (one u64 offset, or a u32 offset + length)
-    alg_bytes = R * L * 1 + R * 8
-    achieved = alg_bytes / (k_ms * 1e-3) / 1e9
-    traffic = None
-    pmc = os.path.join(ROOT, "profiles", "pmc_summary.json")
-    if os.path.exists(pmc):
-        try:
-            with open(pmc) as f:
-                pj = json.load(f)
-            for e in (pj if isinstance(pj, list) else [pj]):
-                if (e.get("config", "c2") == args.config and e.get("reads_per_launch", e.get("reads")) == R
-                        and e.get("read_len") == L and e.get("k") == k):
-                    traffic = e.get("hbm_bytes_per_launch")
-        except (OSError, ValueError, AttributeError):
-            pass
-    detail["kernel_ms"] = kernel_ms
+    k_steps = k_elapsed = k_value = k_kmer_rate = k_ms = alg_bytes = achieved = traffic = None
+    dump = None               # what the last timed step computed (--dump-outputs): counts, totals
+    if args.full or not headline:
+        counts = torch.zeros(2 * n_pat, dtype=torch.int32, device=dev)
+        tally = torch.zeros(1, dtype=torch.int64, device=dev)
+        k_steps, k_warm = (args.kernel_steps, 2) if headline else (args.steps, args.warmup)
+        k_elapsed, kernel_ms = kernel_leg(kmap, d_seq, d_offs, d_lens, R, L, k_steps, k_warm, world, dist, counts,
+                                          tally)
+        k_value = reads_total * L * k_steps / k_elapsed / 1e6
+        k_kmer_rate = int(tally.item()) * k_steps / k_elapsed
+        k_ms = float(np.mean(kernel_ms))
+        # algorithmic bytes as SURVEY.md section 8(d) defines them: 1 B per base +
+        # 8 B per read (one u64 offset, or a u32 offset + length)
+        alg_bytes = R * L * 1 + R * 8
+        achieved = alg_bytes / (k_ms * 1e-3) / 1e9
+        pmc = os.path.join(ROOT, "profiles", "pmc_summary.json")
+        if os.path.exists(pmc):
+            try:
+                with open(pmc) as f:
+                    pj = json.load(f)
+                for e in (pj if isinstance(pj, list) else [pj]):
+                    if (e.get("config", "c2") == args.config and e.get("reads_per_launch", e.get("reads")) == R
+                            and e.get("read_len") == L and e.get("k") == k):
+                        traffic = e.get("hbm_bytes_per_launch")
+            except (OSError, ValueError, AttributeError):
+                pass
+        detail["kernel_ms"] = kernel_ms
+        if not headline:
+            dump = (counts.cpu().numpy().view(np.uint32), [int(tally.item())])
 
     # ---- live parity on a bounded sample, at every world size: every rank
     # counts the same first reads of rank 0's files (an equal share of each
@@ -944,6 +1026,8 @@ def main():
                                      n_pat, detail=e2e_detail)
         if rank == 0:
             detail["e2e"] = e2e_detail
+            dump = (e_counts, [e2e["kmers"], e2e["seqs"], e2e["bases"]])
+        if rank == 0 and args.full:
             # full-size self-consistency: the files' counts (all ranks' ranges,
             # all-reduced) == vc_count_device over the same HBM reads
             kmap.reset()
@@ -964,6 +1048,7 @@ def main():
                     detail["cli"] = cli_detail
                 except Exception as e:
                     log("cli leg failed: %r" % (e,))
+        if rank == 0:
             for path in fq_paths:
                 os.unlink(path)
             if work != tmp:
@@ -984,6 +1069,8 @@ def main():
         except OSError as e:
             log("detail record not written: %r" % (e,))
             detail_path = None
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, *dump)
         if headline:
             workload = ("%s: %d file(s) of %dM x %d bp reads (%.2f GB, page cache), k=%d, %s panel (%d patterns, "
                         "%d keys), f_snp=%g; %d rank(s), byte ranges of each file" % (

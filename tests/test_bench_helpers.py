@@ -64,6 +64,26 @@ def test_fastq_bytes_np_equals_fastq_bytes():
         assert S.fastq_bytes_np(reads, first) == S.fastq_bytes(reads, first), first
 
 
+def test_write_fastq_places_every_piece(tmp_path):
+    """bench.write_fastq_from_device writes its pieces at computed offsets, by
+    several threads: the file is the bytes of the per-record writer, across
+    read-number digit boundaries, odd piece sizes and a last short piece."""
+    import torch
+    import bench
+    import vafc_synth as S
+    assert [bench.digits_total(m) for m in (0, 1, 10, 11, 100, 1001)] == [0, 1, 10, 12, 190, 2894]
+    rng = np.random.default_rng(5)
+    for n, L, first, step in ((2500, 150, 9_000, 700), (1203, 37, 0, 100), (5, 150, 99_999_997, 2), (1, 21, 0, 500_000)):
+        reads = np.frombuffer(b"ACGTN", np.uint8)[rng.integers(0, 5, (n, L))]
+        path = str(tmp_path / ("w%d.fq" % n))
+        with open(path, "wb") as f:    # an existing longer file is replaced
+            f.write(b"x" * (n * (2 * L + 40)))
+        bench.write_fastq_from_device(torch.from_numpy(reads.reshape(-1).copy()), n, L, path, threads=3, first=first,
+                                      step=step)
+        with open(path, "rb") as f:
+            assert f.read() == S.fastq_bytes(reads, first), (n, L, first, step)
+
+
 def test_vaf_counts_reads_the_writer_output(tmp_path):
     """bench.vaf_counts parses the .vaf writer's counts back (the N > 1 parity
     compares all-reduced counts with N x the reference's)."""
@@ -171,6 +191,41 @@ def test_bench_line_stays_under_bound():
     a["cli"] = None
     line = bench.assemble_line(a)
     assert line["value_kind"] == "kernel_hbm" and line["value"] == 2992613.2 and line["vs_cpu_baseline"] is None
+
+
+def test_plain_bench_line_keeps_the_headline_and_nulls_the_rest():
+    """A run without --full measures the headline alone: value, ms_per_step and
+    the descriptive keys are those of the full line; the legs it did not run
+    (roofline, CPU baseline, CLI, parity) are null."""
+    import bench
+    full = bench.assemble_line(_fake_measurements())
+    a = _fake_measurements()
+    for key in ("k_value", "k_elapsed", "k_steps", "k_kmer_rate", "k_ms", "achieved", "traffic", "alg_bytes",
+                "cli", "cpu", "parity", "full_parity"):
+        a[key] = None
+    line = bench.assemble_line(a)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup",
+                "value_kind", "kmers_per_sec", "e2e"):
+        assert line[key] == full[key], key
+    assert line["ms_per_step"] == round(10.6363 / 20 * 1e3, 3)
+    for key in ("roofline", "cpu_baseline", "vs_cpu_baseline", "cli", "parity_vs_reference_on_sample",
+                "parity_full_size"):
+        assert line[key] is None, key
+    assert list(line) == list(full)
+
+
+def test_dump_outputs_are_exact_float64(tmp_path):
+    """--dump-outputs: counts.npy and totals.npy hold the uint32 counts and the
+    64-bit totals exactly, as float64."""
+    import bench
+    counts = np.array([0, 1, 2 ** 32 - 1, 123456789], np.uint32)
+    totals = [12729660835, 100000000, 15000000000]
+    d = str(tmp_path / "out" / "dir")
+    bench.dump_outputs(d, counts, totals)
+    c, t = np.load(os.path.join(d, "counts.npy")), np.load(os.path.join(d, "totals.npy"))
+    assert c.dtype == np.float64 and t.dtype == np.float64
+    assert np.array_equal(c.astype(np.uint32), counts) and [int(x) for x in t] == totals
+    assert sorted(os.listdir(d)) == ["counts.npy", "totals.npy"]
 
 
 def test_bench_line_withholds_value_when_ranges_do_not_chain():

@@ -9,9 +9,9 @@ TAG=${1:?tag}
 R=$(pwd)
 O=$R/gpurun_out
 mkdir -p "$O"
-timeout -k 10 400 python bench.py > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err"
-timeout -k 10 300 python bench.py --config c3 --no-cpu --no-e2e > "$O/${TAG}_bench_c3.json" 2> "$O/${TAG}_bench_c3.err"
-timeout -k 10 300 python bench.py --config c5 --no-cpu --no-e2e > "$O/${TAG}_bench_c5.json" 2> "$O/${TAG}_bench_c5.err"
+timeout -k 10 400 python bench.py --full > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err"
+timeout -k 10 300 python bench.py --full --config c3 --no-cpu --no-e2e > "$O/${TAG}_bench_c3.json" 2> "$O/${TAG}_bench_c3.err"
+timeout -k 10 300 python bench.py --full --config c5 --no-cpu --no-e2e > "$O/${TAG}_bench_c5.json" 2> "$O/${TAG}_bench_c5.err"
 cd /tmp
 export TMPDIR=/tmp
 for C in c2 c5; do

@@ -7,10 +7,10 @@ set -o pipefail
 TAG=${1:-r04_final}
 R=$(pwd); O=$R/gpurun_out
 step() { local lim=$1; shift; timeout -k 10 "$lim" "$@" || { echo "STEP FAILED ($?): $*"; exit 1; }; }
-step 600 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+step 600 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 cat $O/${TAG}_bench.json | cut -c1-400
-step 300 python bench.py --config c5 --no-cpu --no-e2e > $O/${TAG}_bench_c5.json 2> $O/${TAG}_bench_c5.err
-step 300 python bench.py --config c3 --no-cpu --no-e2e > $O/${TAG}_bench_c3.json 2> $O/${TAG}_bench_c3.err
+step 300 python bench.py --full --config c5 --no-cpu --no-e2e > $O/${TAG}_bench_c5.json 2> $O/${TAG}_bench_c5.err
+step 300 python bench.py --full --config c3 --no-cpu --no-e2e > $O/${TAG}_bench_c3.json 2> $O/${TAG}_bench_c3.err
 cd /tmp && export TMPDIR=/tmp
 for C in c2 c5; do
   step 300 rocprofv3 --kernel-trace --stats -d $O/${TAG}_prof_$C -o p --output-format csv -- \
