@@ -126,8 +126,8 @@ VC_HD uint32_t vc_l2f_mask(uint32_t h2)
 }
 
 /* The same filter keyed by the two strands' low 32 bits instead of the
- * canonical k-mer (the large-panel kernels, VC_KV_BIG; -DVC_BIG_RAWQ restores
- * the round-4 form for A/B): the queue holds (rlo << 32) | flo, which the drain
+ * canonical k-mer (the large-panel kernels, VC_KV_BIG): the queue holds
+ * (rlo << 32) | flo, which the drain
  * tests with two multiplies and no reverse complement; only survivors rebuild
  * the canonical k-mer (vc_canon_from_strands).  Symmetric in (flo, rlo), so it is a
  * function of the canonical k-mer.  Word from the top bits of one mix, bits

@@ -407,7 +407,6 @@ extern "C" int vc_create(vc_ctx **out, int k, const uint64_t *keys, const uint32
 			fw.swap(fbig);
 			c->big = 1;
 			c->qcap = VC_BIG_QCAP;
-#ifndef VC_BIG_RAWQ
 			// the big kernels queue both strands' low words: key the second
 			// level by them (vc_l2s_*) instead of the canonical k-mer
 			std::fill(l2w.begin(), l2w.end(), 0u);
@@ -416,7 +415,6 @@ extern "C" int vc_create(vc_ctx **out, int k, const uint64_t *keys, const uint32
 					const uint32_t flo = (uint32_t)e.key, rlo = (uint32_t)vc_revcomp(e.key, k);
 					l2w[vc_l2s_hash(flo, rlo) >> (32 - l2bits)] |= vc_l2f_mask(vc_l2s_hash2(flo, rlo));
 				}
-#endif
 		}
 		if (k >= VC_FLANK_MIN_K && !l2bits && !force_bloom) {
 			std::vector<uint32_t> fb((size_t)1 << VC_FLANK_WBITS, 0);

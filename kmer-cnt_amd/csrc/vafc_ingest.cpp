@@ -795,9 +795,10 @@ int vc_ingest_text(VcIngestSource &src, int k, int block_bases, int threads, int
 	}
 	if (prof_print) {
 		const VcIngestProfile &L = vc_ingest_last;
-		fprintf(stderr, "[ingest] %llu pieces, %d threads: total %.3f s; main: wait %.3f submit %.3f reparse %.3f "
-		        "cpu %.3f; workers: parse %.3f slot-wait %.3f acquire %.3f (thread-seconds); parse split: read %.3f "
-		        "(%.2f GB) copy %.3f (%.2f GB, mode %d) guess %.3f; workers cpu %.3f of wall %.3f\n",
+		// microseconds: a small file's copies take less than a millisecond in all
+		fprintf(stderr, "[ingest] %llu pieces, %d threads: total %.6f s; main: wait %.6f submit %.6f reparse %.6f "
+		        "cpu %.6f; workers: parse %.6f slot-wait %.6f acquire %.6f (thread-seconds); parse split: read %.6f "
+		        "(%.2f GB) copy %.6f (%.2f GB, mode %d) guess %.6f; workers cpu %.6f of wall %.6f\n",
 		        (unsigned long long)np, threads, L.total, t_wait, t_submit, t_reparse, L.main_cpu, L.parse,
 		        L.slot_wait, L.acquire, L.read_s, L.read_bytes / 1e9, L.copy_s, L.copy_bytes / 1e9, L.copy_mode,
 		        L.guess_s, L.worker_cpu, L.worker_wall);

@@ -15,47 +15,49 @@
 //  * One lane per read, one wave = 64 reads, 1024-thread persistent blocks
 //    (one per CU, 16 waves/CU) grid-striding over groups of 1024 reads.
 //  * Read bytes are fetched as dwords from the read's 4-byte-aligned start and
-//    realigned with v_alignbyte; 16 bases (one "chunk") per loop trip, with
-//    the next chunk's dwords in flight during the current one.
+//    realigned with v_alignbyte, 16 bases (one "chunk") at a time.
 //  * Decode is SWAR on 4 bytes at a time with v_perm_b32 as a 8-entry LUT --
 //    the same nibble table as the reference's PSHUFB; the reference decodes
 //    the last len%16 bytes of a read with seq_nt4_table instead, so the lane
 //    switches to an exact SWAR seq_nt4_table for that tail chunk.
-//  * Rolling forward / reverse-complement k-mers in 64-bit registers; validity
-//    from a 32-bit shift register of invalid-base flags (a window is valid iff
-//    its last k flags are zero) -- equivalent to the reference's reset-on-N.
-//  * Every valid canonical k-mer probes a blocked Bloom filter held in LDS
-//    (2 bits in one 32-bit word, up to 128 KiB).  Filter hits are compacted
-//    per wave into an LDS queue (ballot + mbcnt); a full queue is drained by
-//    all 64 lanes probing the exact HBM/L2-resident table at once, and hits do
-//    atomicAdd on uint32 counts[(pattern<<1)|is_alt].
+//  * Two scan loops.  k in 16..31 (compile-time K): scan_span_quad packs each
+//    chunk into 2-bit streams, takes every window's strands with v_alignbit
+//    and tracks validity per chunk; four chunks per trip, the next four
+//    chunks' 64 bytes in flight.  Other k (K = 0): scan_span rolls forward /
+//    reverse-complement k-mers base by base, validity from a 32-bit shift
+//    register of invalid-base flags (a window is valid iff its last k flags
+//    are zero) -- both equivalent to the reference's reset-on-N.
+//  * Every valid window is tested against a prefilter held in LDS, chosen by
+//    the host per key set; for k >= VC_FLANK_MIN_K the kernel kind is part of
+//    the template parameter ABL:
+//      - default: a blocked Bloom filter, 2 bits in one 32-bit word, a power
+//        of two of words up to 128 KiB;
+//      - VC_KV_FLANK (small panels): a bitmap of the keys' 10-mers, one byte
+//        lookup per base, a window passes iff four of its 10-mers are set;
+//      - VC_KV_BIG (large panels): the blocked Bloom filter at 144 KiB
+//        (VC_BIG_FILTER_WORDS, not a power of two) with shorter queues.
+//  * Filter passes are compacted per wave into an LDS queue of forward k-mers
+//    (ballot + mbcnt).  The queue is drained at the end of a read group once
+//    it is nearly full (queue_flush), and from its top 64 entries when an
+//    append fills it (queue_append): all 64 lanes probe the exact HBM/L2-
+//    resident table at once, large key sets through a second-level filter in
+//    L2 first, and hits do atomicAdd on uint32 counts[(pattern<<1)|is_alt].
+//    The large-panel kernels leave a near-full drain's second-level gathers
+//    in flight under the scan (drain_pipe).
 //  * Reads longer than VC_LONG_READ are appended to a list and counted by a
 //    second kernel in which every lane of the grid takes a VC_LONG_SEG-base
 //    segment (plus a k-1 halo) of the read.
+//  * Ablation builds (-DVC_ABLATION, make ablation; never shipped) add
+//    kernels for k = 21 whose ABL also carries ablation bits (VAFC_ABLATE):
+//    1 = no LDS filter reads, 4 = no queue appends, 64 = a drain per read
+//    group, 1024 / 2048 / 4096 = the drain decomposition (VC_ABL_*).  Their
+//    results are wrong by design.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "vafc_common.h"
 #include "vafc_internal.h"
 
 #define WAVE 64
-
-// Build-time A/B knobs (make XFLAGS=...; tools/ab_libs.sh): the round-2 forms
-// of two parts of the flank kernels, kept for comparison.
-#ifdef VC_FLANK_WORD
-#define VC_FLANK_U8 0          // flank lookups: 32-bit words, per-base extraction
-#else
-#define VC_FLANK_U8 1          // flank lookups: bytes, two v_bfe_u32 of one register
-#endif
-#ifdef VC_DEFER_BIG
-#define VC_KV_BIG_DEFER VC_KV_BIG   // large-panel kernels: one hit loop per chunk pair
-#else
-#define VC_KV_BIG_DEFER 0
-#endif
-#ifdef VC_SCAN_BWD
-#define VC_SCAN_FB 1           // odd lanes scan backwards (scan_span_quad_fb; measured slower)
-#else
-#define VC_SCAN_FB 0           // every lane scans forwards (the quad loop)
-#endif
 
 // ---------------------------------------------------------------------------
 // small helpers
@@ -100,13 +102,12 @@ __device__ __forceinline__ uint32_t dec_head(uint32_t b)
 
 // The same without the byte-bit-3 term: codes, and bit 2 for the nibbles the
 // LUT marks invalid.  The packed scan tests bit 3 of the raw bytes once per
-// chunk instead of once per dword (dec_bit3) and folds it in only on the rare
-// invalid-base path.
+// chunk instead of once per dword (anyinv in packed_chunk) and folds it in
+// only on the rare invalid-base path (invalid_flags).
 __device__ __forceinline__ uint32_t dec_code(uint32_t b)
 {
 	return __builtin_amdgcn_perm(NIB_HI, NIB_LO, b & 0x07070707u);
 }
-__device__ __forceinline__ uint32_t dec_bit3(uint32_t b) { return (b >> 1) & 0x04040404u; }
 
 // Tail decode = seq_nt4_table (vaf-counter.c:73-90) on 4 bytes: ACGTU/acgtu
 // keep their nibble code, bytes 0..3 map to themselves, all else invalid.
@@ -192,18 +193,11 @@ __device__ __forceinline__ uint32_t ldw(const uint32_t *__restrict__ s32, uint64
 // when all four are inside the buffer, else four clamped dword loads (the
 // last reads of a batch).  Loaded bytes past a read's end are masked later.
 typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
-// The read stream's 16-byte loads.  -DVC_NT_READS (A/B): non-temporal loads,
-// meant to keep the streamed reads from pushing the second-level filter out of
-// the L2 -- but a lane's consecutive chunk loads share cache lines, which the
-// non-temporal loads lose: C5 10.58 -> 12.19 ms, C2 4.91 -> 7.70 ms
-// (profiles/r05v_ab.log, r05w_ab.log).
+// The read stream's 16-byte loads: plain loads.  A lane's consecutive chunk
+// loads share cache lines, which non-temporal loads lose (measured: DESIGN.md).
 __device__ __forceinline__ u32x4a4 ld16(const uint32_t *__restrict__ p)
 {
-#ifdef VC_NT_READS
-	return __builtin_nontemporal_load(reinterpret_cast<const u32x4a4 *>(p));
-#else
 	return *reinterpret_cast<const u32x4a4 *>(p);
-#endif
 }
 __device__ __forceinline__ void ld4(const uint32_t *__restrict__ s32, uint64_t i, uint64_t wmax,
                                     uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d)
@@ -242,8 +236,8 @@ __device__ __forceinline__ uint64_t revcomp_dev(uint64_t x, int k)
 	return (~r) >> (64 - 2 * k);
 }
 
-// Ablation bits of the drain (VC_ABLATION builds only, with ABL 1/2/4 above;
-// results are wrong by design): 1024 = queued entries are dropped, never
+// Ablation bits of the drain (VC_ABLATION builds only, beside the scan's 1, 4
+// and 64; results are wrong by design): 1024 = queued entries are dropped, never
 // drained; 2048 = the drain computes every entry's second-level word and
 // mask but issues no gather and probes nothing; 4096 = the second-level
 // gather runs, survivors are not probed in the exact table.
@@ -251,40 +245,26 @@ __device__ __forceinline__ uint64_t revcomp_dev(uint64_t x, int k)
 #define VC_ABL_NOGATHER 2048
 #define VC_ABL_NOPROBE 4096
 
-// key: the raw forward k-mer (bits above 2k may hold older bases).
-__device__ __forceinline__ void probe_and_count(const VcKernelArgs &A, uint64_t fwd_raw)
-{
-	const uint64_t f = fwd_raw & A.kmask;
-	const uint64_t r = revcomp_dev(f, A.k);
-	const uint64_t key = f < r ? f : r;
-	uint32_t s = vc_table_slot(vc_hash(key), A.tbits);
-	for (;;) {
-		const uint4 e = *reinterpret_cast<const uint4 *>(&A.table[s]);
-		const uint64_t k2 = ((uint64_t)e.y << 32) | e.x;
-		if (k2 == key) {
-			atomicAdd(&A.counts[e.z], 1u);
-			break;
-		}
-		if (k2 == VC_EMPTY_KEY) break;
-		s = (s + 1u) & A.tmask;
-	}
-}
-
+// A wave's queue of filter hits: raw forward k-mers (bits above 2k may hold
+// older bases; every drain masks them or reads only bits below 2k).
 struct WaveQueue {
 	uint64_t *q;     // LDS, A.qcap entries
 	uint32_t n;      // wave-uniform fill
 	// drain_pipe (large-panel kernels): the previous near-full drain's
 	// entries, one per lane, whose second-level words are still in flight
-	uint64_t pe[2];     // the entries (VC_PIPE_ROUNDS of them per lane)
-	uint32_t pm[2], pw[2];  // their filter masks and filter words (empty: pm = 1, pw = 0)
+	uint64_t pe;        // the lane's entry
+	uint32_t pm, pw;    // its filter mask and filter word
 	bool pend;          // wave-uniform: pe / pm / pw hold a drain
 };
 
-// Probe the exact table for queue entries [lo, hi) (up to 4 per lane); the
-// first table load of every entry is issued before any is resolved, so one
-// memory latency covers the whole drain.
-// Large key sets: every entry is first checked against the second-level
-// filter (one L2-resident dword), and only survivors probe the exact table.
+// ABL carries the kernel kind (VC_KV_FLANK, VC_KV_BIG) plus, in ablation builds, the ablation bits.
+// The kernel kind decides the drain: large-panel kernels pipeline their
+// near-full drains (drain_pipe) unless an ablation takes the drain or its
+// gather away.
+constexpr bool vc_big(int ABL) { return (ABL & VC_KV_BIG) != 0; }
+constexpr bool vc_pipe(int ABL) { return vc_big(ABL) && (ABL & (VC_ABL_NODRAIN | VC_ABL_NOGATHER)) == 0; }
+
+// Probe the exact table for one key whose hash is h; hits count.
 template <int ABL>
 __device__ __forceinline__ void probe_key(const VcKernelArgs &A, uint64_t key, uint32_t h)
 {
@@ -305,6 +285,9 @@ __device__ __forceinline__ void probe_key(const VcKernelArgs &A, uint64_t key, u
 	}
 }
 
+// Large key sets: every entry of [lo, hi) is first checked against the
+// second-level filter (one L2-resident dword), and only survivors probe the
+// exact table.
 template <int ABL>
 __device__ __forceinline__ void drain_range_l2f(const VcKernelArgs &A, const uint64_t *q, uint32_t lo,
                                              uint32_t hi, int lane)
@@ -356,56 +339,24 @@ __device__ __forceinline__ uint64_t vc_canon_from_strands(uint32_t flo, uint32_t
 	return f < r ? f : r;
 }
 
-#ifdef VC_BIG_RAWQ   // A/B: the large-panel kernels queue forward k-mers like the others (round 4)
-#define VC_SYMQ(ABL) false
-#else
-#define VC_SYMQ(ABL) (((ABL) & VC_KV_BIG) != 0)
-#endif
-// The hit loops queue the forward k-mer's high word unmasked (bits above 2k
-// hold older bases): every drain masks the entry with A.kmask, and the
-// large-panel drain reads only bits below 2k (the low word and bits
-// 2(k - 16) .. 2k of the entry).  -DVC_HIT_MASK (A/B) masks it in the loop.
-#ifdef VC_HIT_MASK
-#define VC_HIT_HIM HIM
-#else
-#define VC_HIT_HIM (HIM | ~0u)
-#endif
-#ifdef VC_BIG_DRAIN_ALL
-#define VC_DRAIN_ALL 1
-#else
-#define VC_DRAIN_ALL 0
-#endif
-#ifdef VC_NO_DEFER_PROBE   // A/B: near-full drains probe their survivors at once (round 4)
-#define VC_DEFER_PROBE 0
-#else
-#define VC_DEFER_PROBE 1
-#endif
-
-// Large-panel kernels (VC_SYMQ): the second-level filter is keyed by the two
+// Large-panel kernels (vc_big): the second-level filter is keyed by the two
 // strands' low words (vc_l2s_*).  The queue holds the forward k-mer as every
 // kernel queues it; the drain takes flo = its low word and rlo = the reverse
 // complement of its first sixteen bases (one v_alignbit at a run-time shift
 // and a 16-base reverse complement), with no 64-bit reverse complement,
 // canonical minimum or 64-bit hash; only survivors rebuild the canonical
 // k-mer (vc_canon_from_strands) and hash it for the exact table.
-// A near-full drain (KEEP) does not probe its survivors: it writes them back
-// at the bottom of the drained range and returns how many, so that they wait
-// in the queue for the read group's final drain, where one probe latency
-// covers them all, instead of costing this drain a dependent table load.
-// When more survive than `room` entries (a read set dense in keys), they are
-// probed at once.  The final drain (KEEP = false) probes every survivor.
-template <int ABL, bool KEEP>
-__device__ __forceinline__ uint32_t drain_range_sym(const VcKernelArgs &A, uint64_t *q, uint32_t lo,
-                                                    uint32_t hi, int lane, uint32_t room)
+// This is the read group's final drain (queue_flush), where one probe latency
+// covers every survivor; near-full queues go through drain_pipe (or, under
+// VC_ABL_NOGATHER, through here as far as the gather that is not issued).
+template <int ABL>
+__device__ __forceinline__ void drain_range_sym(const VcKernelArgs &A, const uint64_t *q, uint32_t lo,
+                                                uint32_t hi, int lane)
 {
-	// rounds of WAVE entries: a near-full drain takes exactly the queue's top
-	// WAVE entries (queue_append), the final drain at most VC_BIG_QCAP (the
-	// large-panel queues), so no round is spent on lanes known to be empty
-	constexpr int NR = (KEEP && !VC_DRAIN_ALL) ? 1 : (int)(VC_BIG_QCAP / WAVE);
-	constexpr bool FULL = KEEP && !VC_DRAIN_ALL;   // every lane holds an entry
+	// rounds of WAVE entries: the large-panel queues hold at most VC_BIG_QCAP
+	constexpr int NR = (int)(VC_BIG_QCAP / WAVE);
 	static_assert(NR >= 1 && NR <= 4, "drain rounds");
 	uint32_t fl[4], rl[4], w[4], m[4];
-	uint64_t e64[4];
 	const uint32_t l2sh = 32u - A.l2bits;
 	const uint32_t fsh16 = 2u * (uint32_t)(A.k - 16);   // the window's first sixteen bases
 #pragma unroll
@@ -414,9 +365,8 @@ __device__ __forceinline__ uint32_t drain_range_sym(const VcKernelArgs &A, uint6
 		fl[r] = rl[r] = 0;
 		w[r] = 0;
 		m[r] = 1;
-		if (FULL || i < hi) {
+		if (i < hi) {
 			const uint64_t e = q[i];
-			e64[r] = e;
 			fl[r] = (uint32_t)e;
 			rl[r] = rc16(__builtin_amdgcn_alignbit((uint32_t)(e >> 32), (uint32_t)e, fsh16));
 			// vc_l2s_hash / vc_l2s_hash2 sharing the strands' two products
@@ -430,59 +380,34 @@ __device__ __forceinline__ uint32_t drain_range_sym(const VcKernelArgs &A, uint6
 			else w[r] = A.l2f[hw >> l2sh];
 		}
 	}
-	if constexpr ((ABL & VC_ABL_NOGATHER) != 0) return 0;
-	bool surv[4];
-#pragma unroll
-	for (int r = 0; r < NR; ++r) surv[r] = (w[r] & m[r]) == m[r];   // false for empty entries (w = 0, m = 1)
-	if constexpr (KEEP && VC_DEFER_PROBE) {
-		uint64_t bal[4];
-		uint32_t n = 0;
-#pragma unroll
-		for (int r = 0; r < NR; ++r) {
-			bal[r] = __ballot(surv[r]);
-			n += (uint32_t)__popcll(bal[r]);
-		}
-		if (n == 0) return 0;
-		if (n <= room) {
-			uint32_t at = lo;
-#pragma unroll
-			for (int r = 0; r < NR; ++r) {
-				const uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[r] >> 32),
-				                                               __builtin_amdgcn_mbcnt_lo((uint32_t)bal[r], 0u));
-				if (surv[r]) q[at + pre] = e64[r];
-				at += (uint32_t)__popcll(bal[r]);
-			}
-			return n;
-		}
-	}
+	if constexpr ((ABL & VC_ABL_NOGATHER) != 0) return;
 #pragma unroll
 	for (int r = 0; r < NR; ++r) {
-		if (!surv[r]) continue;
+		if ((w[r] & m[r]) != m[r]) continue;      // also skips empty entries (w = 0, m = 1)
 		const uint64_t key = vc_canon_from_strands(fl[r], rl[r], A.k);
 		probe_key<ABL>(A, key, vc_hash(key));
 	}
-	return 0;
 }
 
-// Drain queue entries [lo, hi).  KEEP (near-full drains of the large-panel
-// kernels): survivors of the second-level filter may be kept at q[lo ..
-// lo + returned) for a later drain, at most `room` of them; otherwise every
-// entry is resolved and 0 is returned.
-template <int ABL, bool KEEP = false>
-__device__ __forceinline__ uint32_t drain_range(const VcKernelArgs &A, uint64_t *q, uint32_t lo,
-                                                uint32_t hi, int lane, uint32_t room = 0)
+// Drain queue entries [lo, hi) (up to 4 per lane): every entry is resolved.
+// The first load of every entry is issued before any is resolved, so one
+// memory latency covers the whole drain.
+template <int ABL>
+__device__ __forceinline__ void drain_range(const VcKernelArgs &A, const uint64_t *q, uint32_t lo,
+                                            uint32_t hi, int lane)
 {
 	__builtin_amdgcn_wave_barrier();
 	if constexpr ((ABL & VC_ABL_NODRAIN) != 0) {
 		asm volatile("" :: "v"(q[lo + (uint32_t)lane]));
-		return 0;
+		return;
 	}
-	if constexpr (VC_SYMQ(ABL)) {
-		return drain_range_sym<ABL, KEEP>(A, q, lo, hi, lane, room);
+	if constexpr (vc_big(ABL)) {
+		drain_range_sym<ABL>(A, q, lo, hi, lane);
+		return;
 	}
 	if (A.l2bits) {
 		drain_range_l2f<ABL>(A, q, lo, hi, lane);
-		return 0;
+		return;
 	}
 	uint64_t key[4];
 	uint32_t s[4];
@@ -516,7 +441,6 @@ __device__ __forceinline__ uint32_t drain_range(const VcKernelArgs &A, uint64_t 
 			x = *reinterpret_cast<const uint4 *>(&A.table[t]);
 		}
 	}
-	return 0;
 }
 
 // Large-panel kernels: a near-full drain takes the queue's top WAVE entries
@@ -524,14 +448,9 @@ __device__ __forceinline__ uint32_t drain_range(const VcKernelArgs &A, uint64_t 
 // gathers, but tests them only at the NEXT near-full drain (or the final
 // one), so the gathers' latency runs under the scan instead of stalling the
 // wave.  The previous drain's survivors go back into the queue where room
-// allows (as KEEP does), else they are probed at once.  Returns the new
-// fill.  C5 10.43-10.45 -> 10.35-10.37 ms (profiles/r05pp_ab.log);
-// -DVC_NO_PIPE_DRAIN restores drain_range<KEEP> for them.
-#ifndef VC_NO_PIPE_DRAIN
-#define VC_PIPE(ABL) (VC_SYMQ(ABL) && !VC_DRAIN_ALL && ((ABL) & (VC_ABL_NODRAIN | VC_ABL_NOGATHER)) == 0)
-#else
-#define VC_PIPE(ABL) false
-#endif
+// allows (they wait there for the read group's final drain, where one probe
+// latency covers them all), else they are probed at once.  Returns the new
+// fill.  C5 10.43-10.45 -> 10.35-10.37 ms (profiles/r05pp_ab.log).
 template <int ABL>
 __device__ __forceinline__ void pipe_probe(const VcKernelArgs &A, uint64_t e)
 {
@@ -540,71 +459,38 @@ __device__ __forceinline__ void pipe_probe(const VcKernelArgs &A, uint64_t e)
 	const uint64_t key = vc_canon_from_strands(fl, rl, A.k);
 	probe_key<ABL>(A, key, vc_hash(key));
 }
-// VC_PIPE_ROUNDS = 2 (A/B): the drain takes the whole queue (65..128
-// entries, two per lane) instead of its top 64: 10.72 against 10.35 ms
-// (profiles/r05p2_ab.log), not the default.
-#ifndef VC_PIPE_ROUNDS
-#define VC_PIPE_ROUNDS 1
-#endif
 template <int ABL>
 __device__ __forceinline__ uint32_t drain_pipe(const VcKernelArgs &A, WaveQueue &Q, int lane)
 {
-	constexpr int PR = VC_PIPE_ROUNDS;
-	static_assert(PR == 1 || PR == 2, "pipe rounds");
 	__builtin_amdgcn_wave_barrier();
-	const uint32_t lo = PR == 1 ? Q.n - WAVE : 0u;   // PR = 2: Q.n > WAVE, so round 0 is full
-	uint64_t e[PR];
-	uint32_t m[PR], w[PR];
-#pragma unroll
-	for (int r = 0; r < PR; ++r) {
-		const uint32_t i = lo + (uint32_t)(r * WAVE + lane);
-		e[r] = 0;
-		m[r] = 1;
-		w[r] = 0;
-		if (r == 0 || i < Q.n) {
-			e[r] = Q.q[i];
-			const uint32_t fl = (uint32_t)e[r];
-			const uint32_t rl = rc16(__builtin_amdgcn_alignbit((uint32_t)(e[r] >> 32), fl, 2u * (uint32_t)(A.k - 16)));
-			uint32_t u = fl * VC_L2S_M, v = rl * VC_L2S_M;
-			asm("" : "+v"(u), "+v"(v));
-			m[r] = vc_l2f_mask(vc_l2s_mix2(u, v));
-			w[r] = A.l2f[vc_l2s_mix1(u, v) >> (32u - A.l2bits)];   // not awaited here
-		}
-	}
+	const uint32_t lo = Q.n - WAVE;      // Q.n > A.qcap - WAVE >= WAVE: every lane takes an entry
+	const uint64_t e = Q.q[lo + (uint32_t)lane];
+	const uint32_t fl = (uint32_t)e;
+	const uint32_t rl = rc16(__builtin_amdgcn_alignbit((uint32_t)(e >> 32), fl, 2u * (uint32_t)(A.k - 16)));
+	uint32_t u = fl * VC_L2S_M, v = rl * VC_L2S_M;
+	asm("" : "+v"(u), "+v"(v));
+	const uint32_t m = vc_l2f_mask(vc_l2s_mix2(u, v));
+	const uint32_t w = A.l2f[vc_l2s_mix1(u, v) >> (32u - A.l2bits)];   // not awaited here
 	uint32_t n = 0;
 	if (Q.pend) {
-		bool surv[PR];
-		uint64_t bal[PR];
-#pragma unroll
-		for (int r = 0; r < PR; ++r) {
-			surv[r] = (Q.pw[r] & Q.pm[r]) == Q.pm[r];   // false for empty slots (pw = 0, pm = 1)
-			bal[r] = __ballot(surv[r]);
-			n += (uint32_t)__popcll(bal[r]);
-		}
+		const bool surv = (Q.pw & Q.pm) == Q.pm;
+		const uint64_t bal = __ballot(surv);
+		n = (uint32_t)__popcll(bal);
 		if (n) {
+			// kept survivors must leave room for one more full append (<= WAVE)
 			if (n <= A.qcap - WAVE - lo) {
-				uint32_t at = lo;
-#pragma unroll
-				for (int r = 0; r < PR; ++r) {
-					const uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[r] >> 32),
-					                                               __builtin_amdgcn_mbcnt_lo((uint32_t)bal[r], 0u));
-					if (surv[r]) Q.q[at + pre] = Q.pe[r];
-					at += (uint32_t)__popcll(bal[r]);
-				}
+				const uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
+				                                               __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+				if (surv) Q.q[lo + pre] = Q.pe;
 			} else {
-#pragma unroll
-				for (int r = 0; r < PR; ++r)
-					if (surv[r]) pipe_probe<ABL>(A, Q.pe[r]);
+				if (surv) pipe_probe<ABL>(A, Q.pe);
 				n = 0;
 			}
 		}
 	}
-#pragma unroll
-	for (int r = 0; r < PR; ++r) {
-		Q.pe[r] = e[r];
-		Q.pm[r] = m[r];
-		Q.pw[r] = w[r];
-	}
+	Q.pe = e;
+	Q.pm = m;
+	Q.pw = w;
 	Q.pend = true;
 	return lo + n;
 }
@@ -621,13 +507,12 @@ __device__ __forceinline__ void queue_append(const VcKernelArgs &A, WaveQueue &Q
 	if (hit) Q.q[Q.n + pre] = key;
 	Q.n = __builtin_amdgcn_readfirstlane(Q.n + (uint32_t)__popcll(bal));
 	if (Q.n > A.qcap - WAVE) {        // A.qcap >= 2 WAVE
-		if constexpr (VC_PIPE(ABL)) {
+		if constexpr (vc_pipe(ABL)) {
 			Q.n = drain_pipe<ABL>(A, Q, lane);
 		} else {
-			// kept survivors must leave room for one more full append (<= WAVE);
-			// VC_BIG_DRAIN_ALL (A/B): the large-panel kernels drain the whole queue
-			const uint32_t lo = (VC_SYMQ(ABL) && VC_DRAIN_ALL) ? 0u : Q.n - WAVE;
-			Q.n = lo + drain_range<ABL, true>(A, Q.q, lo, Q.n, lane, A.qcap - WAVE - lo);
+			const uint32_t lo = Q.n - WAVE;
+			drain_range<ABL>(A, Q.q, lo, Q.n, lane);
+			Q.n = lo;
 			// leave nothing in flight on this (rare) path, so that the compiler
 			// can keep counting the scan's prefetches across it
 			__builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
@@ -638,23 +523,20 @@ __device__ __forceinline__ void queue_append(const VcKernelArgs &A, WaveQueue &Q
 template <int ABL>
 __device__ __forceinline__ void queue_flush(const VcKernelArgs &A, WaveQueue &Q, int lane)
 {
-	if constexpr (VC_PIPE(ABL)) {
+	if constexpr (vc_pipe(ABL)) {
 		// the pending drain's survivors join the final drain where they fit
 		if (Q.pend) {
-#pragma unroll
-			for (int r = 0; r < VC_PIPE_ROUNDS; ++r) {
-				const bool surv = (Q.pw[r] & Q.pm[r]) == Q.pm[r];
-				const uint64_t bal = __ballot(surv);
-				if (bal) {
-					const uint32_t n = (uint32_t)__popcll(bal);
-					if (Q.n + n <= A.qcap) {
-						const uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
-						                                               __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-						if (surv) Q.q[Q.n + pre] = Q.pe[r];
-						Q.n += n;
-					} else if (surv) {
-						pipe_probe<ABL>(A, Q.pe[r]);
-					}
+			const bool surv = (Q.pw & Q.pm) == Q.pm;
+			const uint64_t bal = __ballot(surv);
+			if (bal) {
+				const uint32_t n = (uint32_t)__popcll(bal);
+				if (Q.n + n <= A.qcap) {
+					const uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
+					                                               __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+					if (surv) Q.q[Q.n + pre] = Q.pe;
+					Q.n += n;
+				} else if (surv) {
+					pipe_probe<ABL>(A, Q.pe);
 				}
 			}
 			Q.pend = false;
@@ -715,12 +597,6 @@ struct Roller {
 	__device__ __forceinline__ bool valid() const { return inv < vthr; }
 };
 
-__device__ __forceinline__ uint64_t canonical_of(uint32_t flo, uint32_t fhi, uint32_t rlo, uint32_t rhi)
-{
-	const uint64_t f = ((uint64_t)fhi << 32) | flo, r = ((uint64_t)rhi << 32) | rlo;
-	return f < r ? f : r;
-}
-
 // ---------------------------------------------------------------------------
 // scan one span of one read per lane, wave-uniform trip count
 // ---------------------------------------------------------------------------
@@ -730,7 +606,7 @@ __device__ __forceinline__ uint64_t canonical_of(uint32_t flo, uint32_t fhi, uin
 // valid position range [vlo, vhi) (vlo = 0, vhi = len for a whole read).
 // The lane's count of valid k-mers accumulates in `tl`.
 // ABL (ablation builds only, -DVC_ABLATION; results are wrong by design):
-//   1 = no LDS filter reads, 2 = no global read-byte loads, 4 = no queue appends
+//   1 = no LDS filter reads, 4 = no queue appends
 template <int K, bool HAS_LO, int ABL = 0>
 __device__ __forceinline__ void scan_span(const VcKernelArgs &A, const uint32_t *__restrict__ s32,
                                           uint64_t wmax, uint64_t off, int len, int c_lo, int c_hi,
@@ -763,13 +639,7 @@ __device__ __forceinline__ void scan_span(const VcKernelArgs &A, const uint32_t 
 		const int c = c_lo + it;
 		// the dwords of the next two chunks are in flight while this one is processed
 		uint32_t y1 = 0, y2 = 0, y3 = 0, y4 = 0;
-		if (c + 2 < c_hi) {
-			if constexpr ((ABL & 2) != 0) {
-				y1 = (uint32_t)wi * 0x9E3779B1u; y2 = y1 ^ 0x41434754u; y3 = y1 + 0x54474341u; y4 = y1 * 5u;
-			} else {
-				ld4(s32, wi + 9, wmax, y1, y2, y3, y4);
-			}
-		}
+		if (c + 2 < c_hi) ld4(s32, wi + 9, wmax, y1, y2, y3, y4);
 		const uint32_t b0 = __builtin_amdgcn_alignbyte(w1, w0, sh);
 		const uint32_t b1 = __builtin_amdgcn_alignbyte(w2, w1, sh);
 		const uint32_t b2 = __builtin_amdgcn_alignbyte(w3, w2, sh);
@@ -849,16 +719,6 @@ __device__ __forceinline__ void scan_span(const VcKernelArgs &A, const uint32_t 
 // are the full forward k-mers of the hit positions extracted (variable
 // shift) and queued.
 
-// 4x4 transpose of 2-bit fields: (byte r, field c) <-> (byte c, field r).
-__device__ __forceinline__ uint32_t transpose2x4x4(uint32_t a)
-{
-	uint32_t t = ((a >> 6) ^ a) & 0x00CC00CCu;
-	a ^= t ^ (t << 6);
-	t = ((a >> 12) ^ a) & 0x0000F0F0u;
-	a ^= t ^ (t << 12);
-	return a;
-}
-
 // Reverse the order of the 16 2-bit fields of a word.
 __device__ __forceinline__ uint32_t pairrev(uint32_t x)
 {
@@ -925,18 +785,17 @@ __device__ __forceinline__ int clamp16(int v) { return v < 0 ? 0 : (v > 16 ? 16 
 
 // Flank-bitmap lookups of one chunk (VC_KV_FLANK): R with bit 15 - j set iff
 // the 10-mer ending at base j (the low 20 bits of the forward stream there) is
-// in the bitmap -- word bits 5..19, bit bits 0..4 (v_bfe_u32 uses the low 5
-// bits of its offset).  5 VALU per base: extraction, shift, mask, test, merge.
-// Bases j < J0 or j >= J1 are not looked up (their bits stay 0).
+// in the bitmap.  Bases j < J0 or j >= J1 are not looked up (their bits stay 0).
 //
-// Byte form (the default; -DVC_FLANK_WORD = the word form below): the bitmap
-// is the same bytes read one byte at a time, byte v >> 3, bit v & 7.  The
-// byte address (bits 3..19 of the 10-mer) and the bit index (bits 0..2) are
+// The bitmap is read one byte at a time, byte v >> 3, bit v & 7 of 10-mer v.
+// The byte address (bits 3..19 of the 10-mer) and the bit index (bits 0..2) are
 // two v_bfe_u32 of ONE register that holds the whole 10-mer: Bc for bases
 // 9..15, B7 = bases -7..8 for bases 7 and 8, B9 = bases -9..6 for bases 0..6
-// (two v_alignbit per chunk).  4 VALU per base plus 2 per chunk, against 5
-// per base: no per-base extraction, and no mask (the byte address needs none;
-// the 32-bit word address needed shift + mask).
+// (two v_alignbit per chunk).  4 VALU per base plus 2 per chunk: no per-base
+// extraction, and no mask (the byte address needs none; reading the bitmap as
+// 32-bit words took a shift and a mask more, 5 VALU per base).  The test bits
+// are merged with one v_lshl_or_b32 per base into two chains (the compiler's
+// own shift + or3 tree costs 1.5 VALU per base).
 template <int J0, int J1, int ABL = 0>
 __device__ __forceinline__ uint32_t flank_bits_u8(uint32_t Bm1, uint32_t Bc)
 {
@@ -957,30 +816,6 @@ __device__ __forceinline__ uint32_t flank_bits_u8(uint32_t Bm1, uint32_t Bc)
 #pragma unroll
 	for (int j = J0; j < J1; ++j) {
 		const uint32_t t = __builtin_amdgcn_ubfe(fb[j], fi[j], 1u);
-		uint32_t &R = (j & 1) ? R1 : R0;
-		asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(R) : "v"(t), "i"(15 - j), "v"(R));
-	}
-	return R0 | R1;
-}
-
-template <int J0, int J1, int ABL = 0>
-__device__ __forceinline__ uint32_t flank_bits(uint32_t fbase, uint32_t Bm1, uint32_t Bc)
-{
-	uint32_t fw[16], fx[16];
-#pragma unroll
-	for (int j = J0; j < J1; ++j) {
-		const uint32_t x = __builtin_amdgcn_alignbit(Bm1, Bc, (uint32_t)(2 * (15 - j)));
-		const uint32_t a = x >> 3;
-		if constexpr ((ABL & 1) != 0) { asm volatile("" :: "v"(a)); fw[j] = a; }
-		else fw[j] = lds_word(fbase, a, ((1u << (2 * VC_FLANK_BASES - 5)) - 1u) << 2);
-		fx[j] = x;
-	}
-	// merged with one v_lshl_or_b32 per base into two chains (the compiler's
-	// own shift + or3 tree costs 1.5 VALU per base)
-	uint32_t R0 = 0, R1 = 0;
-#pragma unroll
-	for (int j = J0; j < J1; ++j) {
-		const uint32_t t = __builtin_amdgcn_ubfe(fw[j], fx[j], 1u);
 		uint32_t &R = (j & 1) ? R1 : R0;
 		asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(R) : "v"(t), "i"(15 - j), "v"(R));
 	}
@@ -1080,7 +915,7 @@ __device__ __forceinline__ uint32_t bloom_bits_big(const VcKernelArgs &A, uint32
 	return hm;
 }
 
-// A chunk's filter lookups issued VC_BIG_GROUP / VC_FLANK_GROUP windows at a
+// A chunk's large-panel filter lookups issued VC_BIG_GROUP windows at a
 // time, each group's bits tested before the next group's lookups issue (an
 // empty asm with a memory clobber keeps the compiler from hoisting them): the
 // live ranges of the looked-up words and their operands shrink (C5 kernel 124
@@ -1088,13 +923,9 @@ __device__ __forceinline__ uint32_t bloom_bits_big(const VcKernelArgs &A, uint32
 // could not keep in registers.  The lookup latency is covered by the other
 // three waves of the SIMD.  C5 10.69-10.73 -> 10.58-10.62 ms with the plain
 // address mask above (profiles/r05o_ab.log, r05p_ab.log; groups of 4 the same);
-// the flank kernel's lookups in groups of 8 or 4 were not faster (r05q_ab.log).
-#ifndef VC_BIG_GROUP
-#define VC_BIG_GROUP 8
-#endif
-#ifndef VC_FLANK_GROUP
-#define VC_FLANK_GROUP 16
-#endif
+// the flank kernel's lookups in groups of 8 or 4 were not faster (r05q_ab.log),
+// so it issues a chunk's sixteen at once.
+constexpr int VC_BIG_GROUP = 8;
 template <int K, int J0, int J1, int ABL>
 __device__ __forceinline__ uint32_t bloom_bits_big_grouped(const VcKernelArgs &A, uint32_t fbase, uint32_t Bm1, uint32_t Bc,
                                                           uint32_t Cm2, uint32_t Cm1, uint32_t Cc)
@@ -1108,18 +939,6 @@ __device__ __forceinline__ uint32_t bloom_bits_big_grouped(const VcKernelArgs &A
 		return h | bloom_bits_big_grouped<K, JM, J1, ABL>(A, fbase, Bm1, Bc, Cm2, Cm1, Cc);
 	}
 }
-template <int J0, int J1, int ABL>
-__device__ __forceinline__ uint32_t flank_bits_u8_grouped(uint32_t Bm1, uint32_t Bc)
-{
-	if constexpr (J1 - J0 <= VC_FLANK_GROUP) {
-		return flank_bits_u8<J0, J1, ABL>(Bm1, Bc);
-	} else {
-		constexpr int JM = J0 + VC_FLANK_GROUP;
-		uint32_t h = flank_bits_u8<J0, JM, ABL>(Bm1, Bc);
-		asm volatile("" : "+v"(h) :: "memory");
-		return h | flank_bits_u8_grouped<JM, J1, ABL>(Bm1, Bc);
-	}
-}
 
 // One 16-base chunk c of the packed scan from its five dwords (w0: the dword
 // holding the chunk's first byte, realigned by sh); (B1, C1) / (B2, C2) are
@@ -1131,7 +950,6 @@ __device__ __forceinline__ uint32_t packed_chunk(const VcKernelArgs &A, int c, i
                                              int &U, int &Qe, uint32_t &H, const uint32_t *__restrict__ filt,
                                              WaveQueue &Q, uint32_t &tl, int lane)
 {
-	constexpr uint32_t HIM = (1u << (2 * K - 32)) - 1u;
 	const uint32_t fsh = A.fsh;
 	const uint32_t wmask4 = ((1u << A.wbits) - 1u) << 2;
 	const uint32_t fbase = lds_base(filt);       // the filter sits at a 16-byte aligned LDS base
@@ -1153,9 +971,8 @@ __device__ __forceinline__ uint32_t packed_chunk(const VcKernelArgs &A, int c, i
 		// flank bitmap (vc_flank_*): one lookup per base, of the 10-mer ending
 		// there; window j passes iff the 10-mers ending at j (its last ten
 		// bases) and at j - (K - 10) (its first ten) are both in the set
-		(void)fsh; (void)wmask4; (void)Cm2;
-		if constexpr (VC_FLANK_U8) hm = flank_bits_u8_grouped<J0, J1, ABL>(Bm1, Bc);
-		else hm = flank_bits<J0, J1, ABL>(fbase, Bm1, Bc);
+		(void)fsh; (void)wmask4; (void)Cm2; (void)fbase;
+		hm = flank_bits_u8<J0, J1, ABL>(Bm1, Bc);
 		const uint32_t P = (H << 16) | hm;           // R of chunks c-1 | c, c-2 in H >> 16
 		hm = flank_windows<K>(hm, H, P);
 		H = P;
@@ -1165,7 +982,7 @@ __device__ __forceinline__ uint32_t packed_chunk(const VcKernelArgs &A, int c, i
 	} else {
 	// pass <=> bits (flo & 31) and (rlo & 31) of the filter word are set:
 	// hm = (hm << 1) | ((w >> flo) & (w >> rlo) & 1), 4 VALU per window
-	// windows j < J0 or j >= J1 are known invalid (see scan_span_packed) and
+	// windows j < J0 or j >= J1 are known invalid (see scan_span_quad) and
 	// not looked up
 	uint32_t fw[16], fl[16], rl[16];
 #pragma unroll
@@ -1220,7 +1037,7 @@ __device__ __forceinline__ uint32_t packed_chunk(const VcKernelArgs &A, int c, i
 			// lowest pass first; lanes without one compute a garbage key they do not append
 			const uint32_t b = (uint32_t)__builtin_ctz(hm | 0x80000000u);   // hm < 2^16
 			const uint32_t flo = __builtin_amdgcn_alignbit(Bm1, Bc, 2u * b);
-			const uint32_t fhi = __builtin_amdgcn_alignbit(Bm2, Bm1, 2u * b) & VC_HIT_HIM;
+			const uint32_t fhi = __builtin_amdgcn_alignbit(Bm2, Bm1, 2u * b);
 			queue_append<ABL>(A, Q, bal, has, ((uint64_t)fhi << 32) | flo, lane);
 			hm &= hm - 1u;
 		}
@@ -1237,11 +1054,10 @@ __device__ __forceinline__ uint32_t packed_chunk(const VcKernelArgs &A, int c, i
 // benchmark panel's pass rate), at 4 VALU per trip to pick the chunk's
 // streams.  v_alignbit uses the low 5 bits of its shift, so 2b serves both
 // halves.
-template <int K, int ABL>
+template <int ABL>
 __device__ __forceinline__ void hit_loop2(const VcKernelArgs &A, WaveQueue &Q, uint32_t hm, uint32_t Bam2,
                                           uint32_t Bam1, uint32_t Ba, uint32_t Bb, int lane)
 {
-	constexpr uint32_t HIM = (1u << (2 * K - 32)) - 1u;
 	if constexpr ((ABL & 4) != 0) {
 		asm volatile("" :: "v"(hm));
 	} else if (__ballot(hm != 0u)) {
@@ -1254,7 +1070,7 @@ __device__ __forceinline__ void hit_loop2(const VcKernelArgs &A, WaveQueue &Q, u
 			const bool ina = b >= 16u;
 			const uint32_t lo = ina ? Ba : Bb, hi = ina ? Bam1 : Ba, hi2 = ina ? Bam2 : Bam1;
 			const uint32_t flo = __builtin_amdgcn_alignbit(hi, lo, 2u * b);
-			const uint32_t fhi = __builtin_amdgcn_alignbit(hi2, hi, 2u * b) & VC_HIT_HIM;
+			const uint32_t fhi = __builtin_amdgcn_alignbit(hi2, hi, 2u * b);
 			queue_append<ABL>(A, Q, bal, has, ((uint64_t)fhi << 32) | flo, lane);
 			hm &= hm - 1u;
 		}
@@ -1269,8 +1085,7 @@ __device__ __forceinline__ void hit_loop2(const VcKernelArgs &A, WaveQueue &Q, u
 template <int K, int ABL>
 __device__ __forceinline__ void packed_streams(const VcKernelArgs &A, int c, int tail_c, int tail_r, int nt4m, uint32_t sh, uint32_t w0, uint32_t w1,
                                                uint32_t w2, uint32_t w3, uint32_t w4, uint32_t &Bm1, uint32_t &Bm2,
-                                               uint32_t &Cm1, uint32_t &Cm2, int &U, int &Qe, uint32_t &H,
-                                               const uint32_t *__restrict__ filt)
+                                               uint32_t &Cm1, uint32_t &Cm2, int &U, int &Qe, uint32_t &H)
 {
 	const uint32_t b0 = __builtin_amdgcn_alignbyte(w1, w0, sh);
 	const uint32_t b1 = __builtin_amdgcn_alignbyte(w2, w1, sh);
@@ -1296,8 +1111,7 @@ __device__ __forceinline__ void packed_streams(const VcKernelArgs &A, int c, int
 		// the first window (ending at K - 1) starts with the 10-mer ending at
 		// base 9: chunk 0's bases 9..15 are looked up for the later windows
 		static_assert(K - VC_FLANK_BASES >= 9, "flank mode needs the first window's head in chunk 0");
-		if constexpr (VC_FLANK_U8) H = flank_bits_u8_grouped<VC_FLANK_BASES - 1, 16, ABL>(Bm1, Bc);
-		else H = flank_bits<VC_FLANK_BASES - 1, 16, ABL>(lds_base(filt), Bm1, Bc);
+		H = flank_bits_u8<VC_FLANK_BASES - 1, 16, ABL>(Bm1, Bc);
 	}
 	Bm2 = Bm1; Bm1 = Bc;
 	Cm2 = Cm1; Cm1 = ~L;
@@ -1349,148 +1163,17 @@ __device__ __forceinline__ void quad_fix(uint32_t sft, uint32_t &a, uint32_t &b,
 
 template <int J> struct J0Tag { static constexpr int value = J; };
 
-// Chunks are processed in pairs.  The 8 dwords of the next pair are requested
-// (two dwordx4 from the same lines, back to back) while the current pair is
-// scanned, so each load has two chunks of work to hide behind.  The steady
-// loop issues the same loads on every trip (lanes past their span re-read
-// harmless bytes), the last pair is peeled: the compiler then waits for a
-// pair's data only when the pair starts.
-template <int K, bool HAS_LO, int ABL = 0, bool SAFE = false>
-__device__ __forceinline__ void scan_span_packed(const VcKernelArgs &A, const uint32_t *__restrict__ s32,
-                                                 uint64_t wmax, uint64_t off, int len, int c_lo, int c_hi,
-                                                 int vlo, int vhi, int nit,
-                                                 const uint32_t *__restrict__ filt, WaveQueue &Q,
-                                                 uint32_t &tl, int lane)
-{
-	static_assert(K >= 16 && K <= 31, "packed scan needs 16 <= k <= 31");
-	// the read's tail chunk decodes with seq_nt4_table (vaf-counter.c:261-291);
-	// in seq_nt4 mode (snp-pattern-gen) every chunk does: tail_c = -1 and the
-	// test (c | -1) == -1 always holds (the OR is scalar in the reads kernel)
-	const int tail_c = A.nt4 ? -1 : ((len & 15) ? (len >> 4) : -1);
-	// seq_nt4 mode decodes all 16 bytes of every chunk with the table: every
-	// dword of the chunk holds "tail" bytes (dec_tail_chunk tests tail_r)
-	const int tail_r = A.nt4 ? 16 : (len & 15);
-	const int nt4m = -(int)A.nt4;   // 0 or -1 (the host stores 0 / 1); kept arithmetic so
-	                                  // the test stays one compare, not (c == tail_c) || nt4
-
-	uint64_t addr = off + 16ull * (uint64_t)c_lo;
-	uint64_t wi = addr >> 2;
-	const uint32_t sh = (uint32_t)(addr & 3u);
-	uint32_t w0, w1, w2, w3, w4, w5, w6, w7, w8;
-	w0 = SAFE ? s32[wi] : ldw(s32, wi, wmax);
-	uint32_t d1 = ldq_s<SAFE>(s32, wi + 1, wmax, w1, w2, w3, w4);
-	uint32_t d5 = ldq_s<SAFE>(s32, wi + 5, wmax, w5, w6, w7, w8);
-	// whole reads, K >= 17: chunk 0 only builds streams (below), so chunk 2's
-	// dwords are needed one chunk after chunk 1's and are requested up front
-	constexpr bool PEEL = !HAS_LO && K >= 17 && (ABL & 32) == 0;
-	[[maybe_unused]] uint32_t x5 = 0, x6 = 0, x7 = 0, x8 = 0, d9 = 0;
-	if constexpr (PEEL) d9 = ldq_s<SAFE>(s32, wi + 9, wmax, x5, x6, x7, x8);
-
-	uint32_t Bm1 = 0, Bm2 = 0, Cm1 = 0, Cm2 = 0;   // streams of the two previous chunks
-	uint32_t H = 0;                                  // flank mode: 10-mer hits of chunks c-2 | c-1
-	int U = 1 - K - vlo + 16 * c_lo;                 // +16 at the top of every chunk
-	int Qe = -vhi + 16 * c_lo;
-
-	[[maybe_unused]] uint32_t abl_sink = 0;
-	int it = 0;
-	// Whole reads, K >= 17: no window ends in chunk 0 (positions 0..15 < K - 1),
-	// so chunk 0 only builds the streams (about 16 % fewer VALU for 150 bp
-	// reads); the pair loop then starts at chunk 1.  The dwords of chunk 1 are
-	// w4..w8 already, chunk 2's were requested with them (x5..x8: requested
-	// here, the large-panel config waited a whole memory latency at chunk 2,
-	// +4.5 %), and everything after moves on by 16 bytes -- the loads stay
-	// within the group's clear range (8 ceil(nit / 2) + 13 dwords from the
-	// first).  A.variant bit 0 turns this off at run time (A/B).
-	if constexpr (PEEL) {
-		if (nit > 0 && (A.variant & 1u) == 0) {
-			quad_fix(d1, w1, w2, w3, w4);
-			packed_streams<K, ABL>(A, c_lo, tail_c, tail_r, nt4m, sh, w0, w1, w2, w3, w4, Bm1, Bm2, Cm1, Cm2, U, Qe, H, filt);
-			w0 = w4; w1 = w5; w2 = w6; w3 = w7; w4 = w8; d1 = d5;
-			w5 = x5; w6 = x6; w7 = x7; w8 = x8; d5 = d9;
-			wi += 4;
-			it = 1;
-		}
-	}
-	auto trip = [&](auto j0tag) {
-		constexpr int J0 = decltype(j0tag)::value;
-		const int c = c_lo + it;
-		uint32_t n0, n1, n2, n3, n4, n5, n6, n7, dn0, dn4;
-		if constexpr ((ABL & 2) != 0) {
-			n0 = (uint32_t)wi * 0x9E3779B1u; n1 = n0 ^ 0x41434754u; n2 = n0 + 0x54474341u; n3 = n0 * 5u;
-			n4 = n0 ^ 0x5A5A5A5Au; n5 = n1 + 7u; n6 = n2 ^ n3; n7 = n4 * 3u;
-			dn0 = dn4 = 0;
-		} else if constexpr ((ABL & 16) != 0) {
-			// timing experiment: issue the real loads but consume them only
-			// after the scan (isolates the cost of waiting from issuing)
-			uint32_t t0_, t1_, t2_, t3_, t4_, t5_, t6_, t7_;
-			ldq(s32, wi + 9, wmax, t0_, t1_, t2_, t3_);
-			ldq(s32, wi + 13, wmax, t4_, t5_, t6_, t7_);
-			abl_sink ^= t0_ ^ t1_ ^ t2_ ^ t3_ ^ t4_ ^ t5_ ^ t6_ ^ t7_;
-			n0 = (uint32_t)wi * 0x9E3779B1u; n1 = n0 ^ 0x41434754u; n2 = n0 + 0x54474341u; n3 = n0 * 5u;
-			n4 = n0 ^ 0x5A5A5A5Au; n5 = n1 + 7u; n6 = n2 ^ n3; n7 = n4 * 3u;
-			dn0 = dn4 = 0;
-		} else if constexpr ((ABL & 8) != 0) {
-			// timing experiment: the memory pattern of a wave-tiled layout
-			// (chunk c of lane l at 16 * (64 c + l) from a wave base)
-			const uint64_t tb = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(off >> 4)) << 2) +
-			                    (uint64_t)(64 * (it + 2) + lane) * 4u;
-			dn0 = ldq(s32, tb, wmax, n0, n1, n2, n3);
-			dn4 = ldq(s32, tb + 256, wmax, n4, n5, n6, n7);
-		} else {
-			dn0 = ldq_s<SAFE>(s32, wi + 9, wmax, n0, n1, n2, n3);
-			dn4 = ldq_s<SAFE>(s32, wi + 13, wmax, n4, n5, n6, n7);
-		}
-		quad_fix(d1, w1, w2, w3, w4);
-		quad_fix(d5, w5, w6, w7, w8);
-		packed_chunk<K, ABL, J0>(A, c, tail_c, tail_r, nt4m, sh, w0, w1, w2, w3, w4, Bm1, Bm2, Cm1, Cm2, U, Qe, H, filt, Q, tl, lane);
-		packed_chunk<K, ABL>(A, c + 1, tail_c, tail_r, nt4m, sh, w4, w5, w6, w7, w8, Bm1, Bm2, Cm1, Cm2, U, Qe, H, filt, Q, tl, lane);
-		w0 = w8;
-		w1 = n0; w2 = n1; w3 = n2; w4 = n3; d1 = dn0;
-		w5 = n4; w6 = n5; w7 = n6; w8 = n7; d5 = dn4;
-		wi += 8;
-	};
-	// chunk 1 of a whole read: its windows end at 16..31, those before K - 1
-	// are invalid, so its first K - 17 filter lookups are skipped
-	// (flank mode looks up every base: chunk 1's are the heads of later windows)
-	if constexpr (!HAS_LO && K >= 18 && (ABL & 32) == 0 && (ABL & VC_KV_FLANK) == 0) {
-		if (it == 1 && it + 2 < nit && (A.variant & 2u) == 0) {
-			trip(J0Tag<K - 17>{});
-			it += 2;
-		}
-	}
-	for (; it + 2 < nit; it += 2) trip(J0Tag<0>{});
-	if constexpr ((ABL & 16) != 0) tl += abl_sink & 1u;
-	if (it < nit) {
-		quad_fix(d1, w1, w2, w3, w4);
-		quad_fix(d5, w5, w6, w7, w8);
-		const bool pair = it + 1 < nit;
-		if (pair)
-			packed_chunk<K, ABL>(A, c_lo + it, tail_c, tail_r, nt4m, sh, w0, w1, w2, w3, w4, Bm1, Bm2, Cm1, Cm2, U, Qe, H, filt, Q,
-			                     tl, lane);
-		// the wave's last chunk: windows j end at 16 cl + j and are valid only
-		// below vhi, so when no lane has more than 8 of them (150-bp reads: 6)
-		// the upper 8 windows are not looked up (A.variant bit 2: always all)
-		const int cl = c_lo + nit - 1;
-		const uint32_t x0 = pair ? w4 : w0, x1 = pair ? w5 : w1, x2 = pair ? w6 : w2, x3 = pair ? w7 : w3,
-		               x4 = pair ? w8 : w4;
-		if ((A.variant & 4u) == 0 && __ballot(vhi - 16 * cl > 8) == 0)
-			packed_chunk<K, ABL, 0, 8>(A, cl, tail_c, tail_r, nt4m, sh, x0, x1, x2, x3, x4, Bm1, Bm2, Cm1, Cm2, U, Qe, H, filt, Q, tl,
-			                           lane);
-		else
-			packed_chunk<K, ABL>(A, cl, tail_c, tail_r, nt4m, sh, x0, x1, x2, x3, x4, Bm1, Bm2, Cm1, Cm2, U, Qe, H, filt, Q, tl,
-			                     lane);
-	}
-}
-
-// The same scan with chunks in quads: each lane requests the next 64 bytes of
-// its read (four dwordx4 from one or two lines, back to back) while the
-// current four chunks are scanned.  Every lane of a wave reads a different
-// read, so every request misses the 32 KiB L1 (16 waves x 64 lanes keep
-// 128 KiB of lines live); the L1's outstanding misses, not instruction issue,
-// bound the pair loop once the flank prefilter cut the VALU per base
+// The packed scan of a span, chunks in quads: each lane requests the next 64
+// bytes of its read (four dwordx4 from one or two lines, back to back) while
+// the current four chunks are scanned.  The steady loop issues the same loads
+// on every trip (lanes past their span re-read harmless bytes) and the last
+// 1..4 chunks are peeled, so the compiler waits for a quad's data only when
+// its chunk starts.  Every lane of a wave reads a different read, so every
+// request misses the 32 KiB L1 (16 waves x 64 lanes keep 128 KiB of lines
+// live); the L1's outstanding misses, not instruction issue, bound a loop of
+// chunk pairs once the flank prefilter cut the VALU per base
 // (TCP_PENDING_STALL_CYCLES 70 % of the kernel).  Four requests to one line
-// back to back cost it one miss instead of two.  A.variant bit 3 selects the
-// pair loop (A/B).
+// back to back cost it one miss instead of two.
 template <int K, bool HAS_LO, int ABL = 0, bool SAFE = false>
 __device__ __forceinline__ void scan_span_quad(const VcKernelArgs &A, const uint32_t *__restrict__ s32,
                                                uint64_t wmax, uint64_t off, int len, int c_lo, int vlo, int vhi,
@@ -1510,7 +1193,10 @@ __device__ __forceinline__ void scan_span_quad(const VcKernelArgs &A, const uint
 	w[0] = SAFE ? s32[wi] : ldw(s32, wi, wmax);
 #pragma unroll
 	for (int q = 0; q < 4; ++q) d[q] = ldq_s<SAFE>(s32, wi + 1 + 4 * q, wmax, w[4 * q + 1], w[4 * q + 2], w[4 * q + 3], w[4 * q + 4]);
-	constexpr bool PEEL = !HAS_LO && K >= 17 && (ABL & 32) == 0;
+	static_assert(K >= 16 && K <= 31, "packed scan needs 16 <= k <= 31");
+	// whole reads, K >= 17: chunk 0 only builds streams (below), so chunk 4's
+	// dwords are needed one chunk early and are requested up front
+	constexpr bool PEEL = !HAS_LO && K >= 17;
 	[[maybe_unused]] uint32_t x0 = 0, x1 = 0, x2 = 0, x3 = 0, dx = 0;
 	if constexpr (PEEL) dx = ldq_s<SAFE>(s32, wi + 17, wmax, x0, x1, x2, x3);
 
@@ -1518,13 +1204,15 @@ __device__ __forceinline__ void scan_span_quad(const VcKernelArgs &A, const uint
 	int U = 1 - K - vlo + 16 * c_lo;
 	int Qe = -vhi + 16 * c_lo;
 	int it = 0;
-	// chunk 0 of a whole read builds only the streams (see scan_span_packed);
-	// the quads then start at chunk 1, chunk 4's dwords requested up front
+	// Whole reads, K >= 17: no window ends in chunk 0 (positions 0..15 < K - 1),
+	// so chunk 0 only builds the streams (about 16 % fewer VALU for 150 bp
+	// reads); the quads then start at chunk 1 and everything moves on by 16 bytes.
+	// A.variant ($VAFC_VARIANT, A/B) bit 0 turns this peel off at run time, bit 1
+	// the chunk-1 skip and bit 2 the half last chunk below.
 	if constexpr (PEEL) {
 		if ((A.variant & 1u) == 0) {
 			quad_fix(d[0], w[1], w[2], w[3], w[4]);
-			packed_streams<K, ABL>(A, c_lo, tail_c, tail_r, nt4m, sh, w[0], w[1], w[2], w[3], w[4], Bm1, Bm2, Cm1, Cm2, U, Qe, H,
-			                       filt);
+			packed_streams<K, ABL>(A, c_lo, tail_c, tail_r, nt4m, sh, w[0], w[1], w[2], w[3], w[4], Bm1, Bm2, Cm1, Cm2, U, Qe, H);
 #pragma unroll
 			for (int i = 0; i < 13; ++i) w[i] = w[i + 4];
 			w[13] = x0; w[14] = x1; w[15] = x2; w[16] = x3;
@@ -1555,21 +1243,15 @@ __device__ __forceinline__ void scan_span_quad(const VcKernelArgs &A, const uint
 #pragma unroll
 		for (int q = 0; q < 4; ++q) quad_fix(d[q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3], w[4 * q + 4]);
 		// flank mode: one hit loop per chunk pair (the Bloom-filter kernels are
-		// at the 128-VGPR limit and would spill; ablation builds: A.variant
-		// bit 6 = per chunk)
-		// (the large-panel Bloom kernels too: VC_DEFER_BIG, A/B)
-		bool defer = (ABL & (VC_KV_FLANK | VC_KV_BIG_DEFER)) != 0;
-#ifdef VC_ABLATION
-		defer = defer && (A.variant & 64u) == 0;
-#endif
-		if constexpr ((ABL & (VC_KV_FLANK | VC_KV_BIG_DEFER)) == 0) defer = false;
+		// at the 128-VGPR limit and would spill)
+		bool defer = (ABL & VC_KV_FLANK) != 0;
 		if (defer) {
 #pragma unroll
 			for (int p = 0; p < 2; ++p) {
 				const uint32_t s2 = Bm2, s1 = Bm1;
 				uint32_t h = p == 0 ? dchunk(j0tag, c, 0) : dchunk(J0Tag<0>{}, c + 2, 8);
 				h = (h << 16) | dchunk(J0Tag<0>{}, c + 2 * p + 1, 8 * p + 4);
-				hit_loop2<K, ABL>(A, Q, h, s2, s1, Bm2, Bm1, lane);
+				hit_loop2<ABL>(A, Q, h, s2, s1, Bm2, Bm1, lane);
 			}
 		} else {
 			chunk(j0tag, J0Tag<16>{}, c, 0);
@@ -1584,7 +1266,10 @@ __device__ __forceinline__ void scan_span_quad(const VcKernelArgs &A, const uint
 		for (int q = 0; q < 4; ++q) d[q] = dn[q];
 		wi += 16;
 	};
-	if constexpr (!HAS_LO && K >= 18 && (ABL & 32) == 0 && (ABL & VC_KV_FLANK) == 0) {
+	// chunk 1 of a whole read: its windows end at 16..31, those before K - 1
+	// are invalid, so its first K - 17 filter lookups are skipped
+	// (flank mode looks up every base: chunk 1's are the heads of later windows)
+	if constexpr (!HAS_LO && K >= 18 && (ABL & VC_KV_FLANK) == 0) {
 		if (it == 1 && it + 4 < nit && (A.variant & 2u) == 0) {
 			trip(J0Tag<K - 17>{});
 			it += 4;
@@ -1598,8 +1283,9 @@ __device__ __forceinline__ void scan_span_quad(const VcKernelArgs &A, const uint
 	if (r >= 2) chunk(J0Tag<0>{}, J0Tag<16>{}, c_lo + it, 0);
 	if (r >= 3) chunk(J0Tag<0>{}, J0Tag<16>{}, c_lo + it + 1, 4);
 	if (r >= 4) chunk(J0Tag<0>{}, J0Tag<16>{}, c_lo + it + 2, 8);
-	// the wave's last chunk: only its lower 8 windows when no lane has more
-	// valid ones (see scan_span_packed)
+	// the wave's last chunk: windows j end at 16 cl + j and are valid only
+	// below vhi, so when no lane has more than 8 of them (150-bp reads: 6)
+	// the upper 8 windows are not looked up
 	const int b = 4 * (r - 1);
 	if (b != 0) {
 		w[0] = b == 4 ? w[4] : (b == 8 ? w[8] : w[12]);
@@ -1615,371 +1301,17 @@ __device__ __forceinline__ void scan_span_quad(const VcKernelArgs &A, const uint
 		chunk(J0Tag<0>{}, J0Tag<16>{}, cl, 0);
 }
 
-// ---------------------------------------------------------------------------
-// flank kernels, whole reads: odd lanes scan their read backwards
-// ---------------------------------------------------------------------------
-//
-// Lane r reads read r, and read r's last bytes share a 128-byte line with
-// read r + 1's first bytes.  Scanned forwards by both lanes, that line is
-// fetched by lane r + 1 at its first trip and by lane r at its last, about
-// 15 us apart, and the L2 has usually dropped it in between (HBM traffic
-// 1.6x the read bytes).  Here odd lanes scan the reverse complement of their
-// read, last chunk first: lane 2i + 1 starts at the line it shares with lane
-// 2i + 2 and ends at the one it shares with lane 2i, so each shared line is
-// requested by both lanes in the same load instruction.
-//
-// A backward lane's chunk c' is read bytes [len - 16c' - 16, len - 16c') of
-// its read, complemented and reversed.  The canonical k-mers, the window
-// validity (in reverse-complement coordinates [0, len)), the tally and the
-// flank test (the bitmap is closed under reverse complement) are unchanged;
-// the queued k-mers are the reverse complements, canonicalised by the drain.
-//
-// Registers: quad q of a window holds the chunk's first four dwords in
-// address order for both directions, w[0] the fifth dword of the window's
-// first chunk (forwards: the dword after, backwards: the dword after, too --
-// which for a backward lane is the first dword of the chunk scanned before).
-// The four realigned dwords in quad order are q0..q3; forwards they are the
-// chunk's bytes 0..15, backwards bytes 12..15, 0..3, 4..7, 8..11 (q1..q3 are
-// the same v_alignbyte for both).  Packing then differs only in per-lane
-// constants: the multiplier (codes reversed inside a byte, or not), one perm
-// selector and the complement (Dir).  Cost: 2 v_cndmask per chunk.
-
-struct Dir {
-	bool bwd;
-	uint32_t mul;     // 0x40100401: a byte's codes reversed (forwards); 0x01041040: in order (backwards)
-	uint32_t sel13;   // perm selector placing dwords q1 and q3
-	uint32_t inv;     // 0 forwards, ~0 backwards (the complement)
-};
-
-// Byte mask of the bytes i >= e of a dword (e <= 0: all, e >= 4: none).
-__device__ __forceinline__ uint32_t bytes_from(int e)
-{
-	return e <= 0 ? 0xFFFFFFFFu : (e >= 4 ? 0u : (0xFFFFFFFFu << (8 * e)));
-}
-
-// Decode of a chunk's four realigned dwords (quad order) with the read's
-// tail rule (vaf-counter.c:261-291): forwards the tail chunk decodes with
-// seq_nt4_table throughout; backwards chunk 0 holds the read's last 16
-// bytes, of which the last len % 16 (its first bytes in scan order:
-// tail_e = 16 - len % 16 in read order) are the tail.
-__device__ __forceinline__ void dec_chunk_fb(const Dir &D, int c, int tail_c, int nt4m, int tail_e, uint32_t q0,
-                                             uint32_t q1, uint32_t q2, uint32_t q3, uint32_t &t0, uint32_t &t1,
-                                             uint32_t &t2, uint32_t &t3)
-{
-	t0 = dec_code(q0); t1 = dec_code(q1); t2 = dec_code(q2); t3 = dec_code(q3);
-	const int cm = c | nt4m;
-	if (__ballot(cm == tail_c)) {
-		if (cm == tail_c) {
-			// read-order dword of q_m: forwards m, backwards (m + 3) & 3
-			const int e = D.bwd ? tail_e : -64;
-			uint32_t mk = bytes_from(e - 12);
-			t0 = (dec_tail(q0) & mk) | (t0 & ~mk);
-			mk = bytes_from(e);
-			t1 = (dec_tail(q1) & mk) | (t1 & ~mk);
-			mk = bytes_from(e - 4);
-			t2 = (dec_tail(q2) & mk) | (t2 & ~mk);
-			mk = bytes_from(e - 8);
-			t3 = (dec_tail(q3) & mk) | (t3 & ~mk);
-		}
-	}
-}
-
-// The chunk's big-endian stream in scan order (see Dir).
-__device__ __forceinline__ uint32_t pack_fb(const Dir &D, uint32_t t0, uint32_t t1, uint32_t t2, uint32_t t3)
-{
-	const uint32_t g0 = (t0 & 0x03030303u) * D.mul;
-	const uint32_t g1 = (t1 & 0x03030303u) * D.mul;
-	const uint32_t g2 = (t2 & 0x03030303u) * D.mul;
-	const uint32_t g3 = (t3 & 0x03030303u) * D.mul;
-	const uint32_t p13 = __builtin_amdgcn_perm(g1, g3, D.sel13);
-	const uint32_t p02 = __builtin_amdgcn_perm(g0, g2, 0x070C030Cu);   // byte 1: q2, byte 3: q0
-	return (p13 | p02) ^ D.inv;
-}
-
-// Invalid bases of the chunk, base j (scan order) at bit 2j; slow path.
-__device__ __forceinline__ uint32_t invalid_bits_fb(const Dir &D, uint32_t t0, uint32_t t1, uint32_t t2, uint32_t t3,
-                                                    uint32_t q0, uint32_t q1, uint32_t q2, uint32_t q3)
-{
-	const uint32_t F = invalid_flags(t0, t1, t2, t3, q0, q1, q2, q3);   // quad-order byte p at bit 2p
-	// backwards: quad order -> read order (rotate by one dword), then reverse
-	return D.bwd ? pairrev(__builtin_amdgcn_alignbit(F, F, 8u)) : F;
-}
-
-template <int K, int ABL, int J0 = 0, int J1 = 16, bool DEFER = false>
-__device__ __forceinline__ uint32_t packed_chunk_fb(const VcKernelArgs &A, const Dir &D, int c, int tail_c, int nt4m,
-                                                    int tail_e, uint32_t q0, uint32_t q1, uint32_t q2, uint32_t q3,
-                                                    uint32_t &Bm1, uint32_t &Bm2, int &U, int &Qe, uint32_t &H,
-                                                    const uint32_t *__restrict__ filt, WaveQueue &Q, uint32_t &tl,
-                                                    int lane)
-{
-	constexpr uint32_t HIM = (1u << (2 * K - 32)) - 1u;
-	uint32_t t0, t1, t2, t3;
-	dec_chunk_fb(D, c, tail_c, nt4m, tail_e, q0, q1, q2, q3, t0, t1, t2, t3);
-	U += 16;
-	Qe += 16;
-	const uint32_t Bc = pack_fb(D, t0, t1, t2, t3);
-	uint32_t hm;
-	if constexpr (VC_FLANK_U8) hm = flank_bits_u8_grouped<J0, J1, ABL>(Bm1, Bc);
-	else hm = flank_bits<J0, J1, ABL>(lds_base(filt), Bm1, Bc);
-	const uint32_t P = (H << 16) | hm;
-	hm = flank_windows<K>(hm, H, P);
-	H = P;
-	uint32_t V = ((1u << clamp16(U)) - 1u) & ~((1u << clamp16(Qe)) - 1u);
-	const uint32_t anyinv = ((t0 | t1 | t2 | t3) & 0x04040404u) | ((q0 | q1 | q2 | q3) & 0x08080808u);
-	if (__ballot(anyinv != 0u)) {
-		if (anyinv != 0u) {
-			const uint32_t F = invalid_bits_fb(D, t0, t1, t2, t3, q0, q1, q2, q3);
-			const int j0 = (int)((uint32_t)__builtin_ctz(F) >> 1);
-			const int j1 = (int)((31u - (uint32_t)__builtin_clz(F)) >> 1);
-			V &= ~((2u << (15 - j0)) - 1u);
-			const int u1 = 16 - j1 - K;
-			U = U < u1 ? U : u1;
-		}
-	}
-	hm &= V;
-	tl += (uint32_t)__builtin_popcount(V);
-	if constexpr (DEFER) {
-		Bm2 = Bm1; Bm1 = Bc;
-		return hm;
-	} else if constexpr ((ABL & 4) != 0) {
-		asm volatile("" :: "v"(hm));
-	} else if (__ballot(hm != 0u)) {
-		for (;;) {
-			const bool has = hm != 0u;
-			const uint64_t bal = __ballot(has);
-			if (!bal) break;
-			const uint32_t b = (uint32_t)__builtin_ctz(hm | 0x80000000u);
-			const uint32_t flo = __builtin_amdgcn_alignbit(Bm1, Bc, 2u * b);
-			const uint32_t fhi = __builtin_amdgcn_alignbit(Bm2, Bm1, 2u * b) & VC_HIT_HIM;
-			queue_append<ABL>(A, Q, bal, has, ((uint64_t)fhi << 32) | flo, lane);
-			hm &= hm - 1u;
-		}
-	}
-	Bm2 = Bm1; Bm1 = Bc;
-	return 0u;
-}
-
-// Chunk 0 of a whole read (no window can end in it, K >= 17): streams only.
-template <int K, int ABL>
-__device__ __forceinline__ void packed_streams_fb(const VcKernelArgs &A, const Dir &D, int c, int tail_c, int nt4m,
-                                                  int tail_e, uint32_t q0, uint32_t q1, uint32_t q2, uint32_t q3,
-                                                  uint32_t &Bm1, uint32_t &Bm2, int &U, int &Qe, uint32_t &H)
-{
-	uint32_t t0, t1, t2, t3;
-	dec_chunk_fb(D, c, tail_c, nt4m, tail_e, q0, q1, q2, q3, t0, t1, t2, t3);
-	U += 16;
-	Qe += 16;
-	const uint32_t anyinv = ((t0 | t1 | t2 | t3) & 0x04040404u) | ((q0 | q1 | q2 | q3) & 0x08080808u);
-	if (__ballot(anyinv != 0u)) {
-		if (anyinv != 0u) {
-			const uint32_t F = invalid_bits_fb(D, t0, t1, t2, t3, q0, q1, q2, q3);
-			const int j1 = (int)((31u - (uint32_t)__builtin_clz(F)) >> 1);
-			const int u1 = 16 - j1 - K;
-			U = U < u1 ? U : u1;
-		}
-	}
-	const uint32_t Bc = pack_fb(D, t0, t1, t2, t3);
-	static_assert(K - VC_FLANK_BASES >= 9, "flank mode needs the first window's head in chunk 0");
-	if constexpr (VC_FLANK_U8) H = flank_bits_u8_grouped<VC_FLANK_BASES - 1, 16, ABL>(Bm1, Bc);
-	else H = flank_bits<VC_FLANK_BASES - 1, 16, ABL>(0u, Bm1, Bc);
-	Bm2 = Bm1; Bm1 = Bc;
-}
-
-// A quad of dwords [q, q + 4) loaded from inside [0, wmax]: a quad that would
-// leave the buffer is loaded from its nearest end and the return value says
-// how far it was moved (positive: back from the end, negative: up from the
-// start); quad_fix_fb shifts the dwords into place.  Dwords outside the
-// buffer are never part of a read.
-__device__ __forceinline__ int ldq_fb(const uint32_t *__restrict__ s32, int64_t q, uint64_t wmax,
-                                      uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d)
-{
-	const int64_t lim = (int64_t)wmax - 3;
-	const int64_t cq = q < 0 ? 0 : (q > lim ? lim : q);
-	const u32x4a4 v = ld16(s32 + cq);
-	a = v.x; b = v.y; c = v.z; d = v.w;
-	const int64_t sft = q - cq;
-	return sft > 3 ? 3 : (sft < -3 ? -3 : (int)sft);
-}
-
-template <bool SAFE>
-__device__ __forceinline__ int ldq_fb_s(const uint32_t *__restrict__ s32, int64_t q, uint64_t wmax,
-                                        uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d)
-{
-	if constexpr (SAFE) {
-		const u32x4a4 v = ld16(s32 + q);
-		a = v.x; b = v.y; c = v.z; d = v.w;
-		return 0;
-	} else {
-		return ldq_fb(s32, q, wmax, a, b, c, d);
-	}
-}
-
-__device__ __forceinline__ void quad_fix_fb(int sft, uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d)
-{
-	if (__ballot(sft != 0)) {        // only the reads at either end of the buffer
-		asm volatile("");
-		// new[s] = old[s + sft] where 0 <= s + sft <= 3 (the rest is outside the buffer)
-		const uint32_t a0 = a, b0 = b, c0 = c, d0 = d;
-		a = sft == 1 ? b0 : (sft == 2 ? c0 : (sft == 3 ? d0 : a0));
-		b = sft == 1 ? c0 : (sft >= 2 ? d0 : (sft == -1 ? a0 : b0));
-		c = sft == 1 ? d0 : (sft == -1 ? b0 : (sft <= -2 ? a0 : c0));
-		d = sft == -1 ? c0 : (sft == -2 ? b0 : (sft == -3 ? a0 : d0));
-	}
-}
-
-template <int K, int ABL = 0, bool SAFE = false>
-__device__ __forceinline__ void scan_span_quad_fb(const VcKernelArgs &A, const uint32_t *__restrict__ s32,
-                                                  uint64_t wmax, uint64_t off, int len, int nit,
-                                                  const uint32_t *__restrict__ filt, WaveQueue &Q, uint32_t &tl,
-                                                  int lane)
-{
-	static_assert(K >= VC_FLANK_MIN_K, "flank kernels only");
-	if (nit == 0) return;
-	Dir D;
-	D.bwd = (lane & 1) != 0 && (A.variant & 256u) == 0;   // A.variant bit 8: all lanes forwards (A/B)
-	D.mul = D.bwd ? 0x01041040u : 0x40100401u;
-	D.sel13 = D.bwd ? 0x0C030C07u : 0x0C070C03u;
-	D.inv = D.bwd ? 0xFFFFFFFFu : 0u;
-	const int nt4m = -(int)A.nt4;
-	const int tail_c = A.nt4 ? -1 : ((len & 15) ? (D.bwd ? 0 : (len >> 4)) : -1);
-	const int tail_e = 16 - (len & 15);
-	// forwards: chunk c at read bytes 16c..; backwards at len - 16c - 16..
-	const int64_t a0 = D.bwd ? (int64_t)off + len - 16 : (int64_t)off;
-	const int64_t x0 = a0 >> 2;                                      // floor, also below 0
-	const uint32_t sh = (uint32_t)(a0 & 3);
-	const int64_t qs = D.bwd ? -4 : 4;                               // dwords per chunk, signed
-	int64_t qb = D.bwd ? x0 : x0 + 1;                                // quad of the window's first chunk
-	uint32_t w[17];
-	int d[4];
-	{
-		const int64_t w0i = D.bwd ? x0 + 4 : x0;
-		const int64_t w0c = w0i < 0 ? 0 : ((uint64_t)w0i > wmax ? (int64_t)wmax : w0i);
-		w[0] = s32[SAFE ? w0i : w0c];
-	}
-#pragma unroll
-	for (int q = 0; q < 4; ++q)
-		d[q] = ldq_fb_s<SAFE>(s32, qb + q * qs, wmax, w[4 * q + 1], w[4 * q + 2], w[4 * q + 3], w[4 * q + 4]);
-	uint32_t x0_ = 0, x1 = 0, x2 = 0, x3 = 0;
-	int dx = ldq_fb_s<SAFE>(s32, qb + 4 * qs, wmax, x0_, x1, x2, x3);
-
-	uint32_t Bm1 = 0, Bm2 = 0, H = 0;
-	int U = 1 - K;
-	int Qe = -len;
-	// realigned dwords of window chunk i (quad order)
-	auto quads = [&](int i, uint32_t &q0, uint32_t &q1, uint32_t &q2, uint32_t &q3) {
-		const uint32_t G = D.bwd ? (i == 0 ? w[0] : w[4 * i - 3]) : w[4 * i + 1];
-		const uint32_t Hh = D.bwd ? w[4 * i + 4] : w[4 * i];
-		q0 = __builtin_amdgcn_alignbyte(G, Hh, sh);
-		q1 = __builtin_amdgcn_alignbyte(w[4 * i + 2], w[4 * i + 1], sh);
-		q2 = __builtin_amdgcn_alignbyte(w[4 * i + 3], w[4 * i + 2], sh);
-		q3 = __builtin_amdgcn_alignbyte(w[4 * i + 4], w[4 * i + 3], sh);
-	};
-	// chunk 0 builds only the streams
-	{
-		quad_fix_fb(d[0], w[1], w[2], w[3], w[4]);
-		uint32_t q0, q1, q2, q3;
-		quads(0, q0, q1, q2, q3);
-		packed_streams_fb<K, ABL>(A, D, 0, tail_c, nt4m, tail_e, q0, q1, q2, q3, Bm1, Bm2, U, Qe, H);
-		const uint32_t e1 = D.bwd ? w[1] : w[4];                    // the fifth dword of chunk 1
-#pragma unroll
-		for (int i = 1; i < 13; ++i) w[i] = w[i + 4];
-		w[0] = e1;
-		w[13] = x0_; w[14] = x1; w[15] = x2; w[16] = x3;
-		d[0] = d[1]; d[1] = d[2]; d[2] = d[3]; d[3] = dx;
-		qb += qs;
-	}
-	if (nit == 1) return;            // wave-uniform
-	int it = 1;
-	auto chunk = [&](auto j1tag, int c, int i) {
-		uint32_t q0, q1, q2, q3;
-		quads(i, q0, q1, q2, q3);
-		packed_chunk_fb<K, ABL, 0, decltype(j1tag)::value>(A, D, c, tail_c, nt4m, tail_e, q0, q1, q2, q3, Bm1, Bm2,
-		                                                    U, Qe, H, filt, Q, tl, lane);
-	};
-	auto dchunk = [&](int c, int i) -> uint32_t {
-		uint32_t q0, q1, q2, q3;
-		quads(i, q0, q1, q2, q3);
-		return packed_chunk_fb<K, ABL, 0, 16, true>(A, D, c, tail_c, nt4m, tail_e, q0, q1, q2, q3, Bm1, Bm2, U, Qe,
-		                                            H, filt, Q, tl, lane);
-	};
-	for (; it + 4 < nit; it += 4) {
-		uint32_t n[16];
-		int dn[4];
-#pragma unroll
-		for (int q = 0; q < 4; ++q)
-			dn[q] = ldq_fb_s<SAFE>(s32, qb + (4 + q) * qs, wmax, n[4 * q], n[4 * q + 1], n[4 * q + 2], n[4 * q + 3]);
-#pragma unroll
-		for (int q = 0; q < 4; ++q) quad_fix_fb(d[q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3], w[4 * q + 4]);
-#pragma unroll
-		for (int p = 0; p < 2; ++p) {
-			const uint32_t s2 = Bm2, s1 = Bm1;
-			uint32_t h = dchunk(it + 2 * p, 2 * p);
-			h = (h << 16) | dchunk(it + 2 * p + 1, 2 * p + 1);
-			hit_loop2<K, ABL>(A, Q, h, s2, s1, Bm2, Bm1, lane);
-		}
-		w[0] = D.bwd ? w[13] : w[16];
-#pragma unroll
-		for (int i = 0; i < 16; ++i) w[i + 1] = n[i];
-#pragma unroll
-		for (int q = 0; q < 4; ++q) d[q] = dn[q];
-		qb += 4 * qs;
-	}
-	// the last 1..4 chunks, all in w already (wave-uniform count)
-#pragma unroll
-	for (int q = 0; q < 4; ++q) quad_fix_fb(d[q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3], w[4 * q + 4]);
-	const int r = nit - it;
-	if (r >= 2) chunk(J0Tag<16>{}, it, 0);
-	if (r >= 3) chunk(J0Tag<16>{}, it + 1, 1);
-	if (r >= 4) chunk(J0Tag<16>{}, it + 2, 2);
-	// the wave's last chunk (window chunk r - 1): only its lower 8 windows when
-	// no lane has more valid ones (see scan_span_packed)
-	const int i = r - 1;
-	if (i != 0) {
-		const uint32_t e = D.bwd ? (i == 1 ? w[1] : (i == 2 ? w[5] : w[9])) : (i == 1 ? w[4] : (i == 2 ? w[8] : w[12]));
-		w[1] = i == 1 ? w[5] : (i == 2 ? w[9] : w[13]);
-		w[2] = i == 1 ? w[6] : (i == 2 ? w[10] : w[14]);
-		w[3] = i == 1 ? w[7] : (i == 2 ? w[11] : w[15]);
-		w[4] = i == 1 ? w[8] : (i == 2 ? w[12] : w[16]);
-		w[0] = e;
-	}
-	const int cl = nit - 1;
-	if ((A.variant & 4u) == 0 && __ballot(len - 16 * cl > 8) == 0)
-		chunk(J0Tag<8>{}, cl, 0);
-	else
-		chunk(J0Tag<16>{}, cl, 0);
-}
-
-// k in 16..31 with a compile-time specialisation: packed streams (the quad
-// loop unless A.variant bit 3 or a memory ablation); otherwise the general
-// rolling scan.
+// k in 16..31 with a compile-time specialisation: packed streams in the quad
+// loop; otherwise the general rolling scan.
 template <int K, bool HAS_LO, int ABL = 0, bool SAFE = false>
 __device__ __forceinline__ void scan_any(const VcKernelArgs &A, const uint32_t *__restrict__ s32,
                                          uint64_t wmax, uint64_t off, int len, int c_lo, int c_hi,
                                          int vlo, int vhi, int nit, const uint32_t *__restrict__ filt,
                                          WaveQueue &Q, uint32_t &tl, int lane)
 {
-	if constexpr (K >= VC_FLANK_MIN_K && (ABL & VC_KV_FLANK) != 0 && !HAS_LO && (ABL & (2 | 8 | 16 | 32)) == 0) {
-		// flank kernels, whole reads, -DVC_SCAN_BWD: odd lanes scan backwards
-		// (A/B only: same time as every lane forwards in the same code, and that
-		// code is 10 % slower than the quad loop)
-		if constexpr (VC_SCAN_FB) {
-			scan_span_quad_fb<K, ABL, SAFE>(A, s32, wmax, off, len, nit, filt, Q, tl, lane);
-			return;
-		}
-	}
-	if constexpr (K >= 16) {
-		if constexpr ((ABL & (2 | 8 | 16)) == 0) {
-#ifdef VC_ABLATION
-			if ((A.variant & 8u) == 0)   // ablation builds: A.variant bit 3 = the pair loop
-#endif
-			{
-				scan_span_quad<K, HAS_LO, ABL, SAFE>(A, s32, wmax, off, len, c_lo, vlo, vhi, nit, filt, Q, tl, lane);
-				return;
-			}
-		}
-		scan_span_packed<K, HAS_LO, ABL, SAFE>(A, s32, wmax, off, len, c_lo, c_hi, vlo, vhi, nit, filt, Q, tl,
-		                                       lane);
-	} else
+	if constexpr (K >= 16)
+		scan_span_quad<K, HAS_LO, ABL, SAFE>(A, s32, wmax, off, len, c_lo, vlo, vhi, nit, filt, Q, tl, lane);
+	else
 		scan_span<K, HAS_LO, ABL>(A, s32, wmax, off, len, c_lo, c_hi, vlo, vhi, nit, filt, Q, tl, lane);
 }
 
@@ -2041,13 +1373,20 @@ vc_count_reads_kernel(VcKernelArgs A)
 		const int nch = (len + 15) >> 4;
 		const int nit = wave_max_i32(nch);
 		uint32_t tl = 0;
-		// the packed scan loads dwords [off/4, off/4 + 8 ceil(nit/2) + 13) (lanes
-		// past their span keep loading); groups clear of the buffer end skip the
-		// per-load clamping
+		// the packed scan (scan_span_quad, nit >= 1) loads dwords off/4 ..
+		// off/4 + max(4 nit + 12, 20): up to off/4 + 20 before its loop (chunk
+		// 0's peel requests a fifth quad), and a trip at chunk `it` <= nit - 5
+		// up to off/4 + 4 it + 32; lanes past their span keep loading.  Waves
+		// clear of the buffer end skip the per-load clamping; the bound tested,
+		// 8 ceil(nit/2) + 13 >= max(4 nit + 13, 21), covers that range.
 		bool clear = (off >> 2) + 8u * (uint64_t)((nit + 1) >> 1) + 13u <= wmax;
 		if constexpr ((ABL & VC_KV_FLANK) != 0) {
-			// backward lanes (scan_span_quad_fb) load dwords down to
-			// (off + len - 16) / 4 - 4 (nit + 2) and up to (off + len) / 4
+			// A leftover of the removed backward scan, whose odd lanes loaded
+			// dwords down to (off + len - 16) / 4 - 4 (nit + 2): no load goes
+			// below off/4 any more, so this term only sends a flank launch's
+			// first read group down the clamped path.  Taking it out changes the
+			// flank kernels' code and was measured with the run-time variant
+			// bits' removal, not on its own.
 			const int64_t xb = ((int64_t)off + len - 16) >> 2;
 			clear = clear && xb - 4 * (int64_t)(nit + 6) >= 0 && (uint64_t)(xb + 4) <= wmax;
 		}
@@ -2142,9 +1481,9 @@ static hipError_t launch_kw(const VcKernelArgs *A, int grid, int grid_long, hipS
 
 #ifdef VC_ABLATION
 #ifdef VC_ABL_SHORT   // the drain decomposition only (compiles in a fraction of the time)
-#define VC_ABL_LIST(X) X(1) X(2) X(4) X(7) X(1024) X(2048) X(4096)
+#define VC_ABL_LIST(X) X(1) X(4) X(1024) X(2048) X(4096)
 #else
-#define VC_ABL_LIST(X) X(1) X(2) X(4) X(3) X(5) X(6) X(7) X(8) X(12) X(16) X(20) X(64) X(1024) X(2048) X(4096)
+#define VC_ABL_LIST(X) X(1) X(4) X(5) X(64) X(1024) X(2048) X(4096)
 #endif
 #endif
 

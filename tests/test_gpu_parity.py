@@ -712,6 +712,46 @@ def test_short_reads_whole_wave(torch_dev):
             assert km == km_want and np.array_equal(got, want)
 
 
+def test_flank_single_partial_group_at_buffer_start(torch_dev):
+    """One flank-kernel launch of a single partial read group (fewer than 1,024
+    reads) on a device buffer that starts with the first read and ends with the
+    last, so the scan's loads run from byte 0 of the buffer to within a dword of
+    its end (the first group of a launch and the buffer's last reads are where
+    the kernel chooses between clamped and unclamped loads).  Lengths 1..40
+    and 150."""
+    import torch
+    import vafc
+    import vafc_synth as S
+    k = 21
+    rng = np.random.default_rng(2107)
+    lens = np.array(list(range(1, 41)) * 8 + [150] * 500 + list(rng.integers(0, 200, 100)))
+    lens = list(rng.permutation(lens)) + [150]
+    assert len(lens) < 1024
+    reads = random_reads(rng, lens)
+    keys, vals, n_pat = table_from_reads(k, reads, rng)
+    want, km_want = oracle_counts(k, keys, vals, n_pat, reads)
+    seq, offs, rl = S.pack_reads(reads)
+    assert offs[0] == 0 and rl[0] > 0 and seq.size == int(offs[-1]) + 150
+    d_seq = torch.from_numpy(seq.copy()).to(torch_dev)
+    d_offs = torch.from_numpy(offs.astype(np.int64)).to(torch_dev)
+    d_lens = torch.from_numpy(rl.astype(np.int32)).to(torch_dev)
+    torch.cuda.synchronize()
+    old = os.environ.get("VAFC_FILTER")
+    os.environ["VAFC_FILTER"] = "flank"
+    try:
+        m = vafc.KmerMap(k, keys, vals, n_pat, 0)
+    finally:
+        if old is None:
+            del os.environ["VAFC_FILTER"]
+        else:
+            os.environ["VAFC_FILTER"] = old
+    m.count_device(d_seq.data_ptr(), seq.size, d_offs.data_ptr(), d_lens.data_ptr(), len(reads))
+    got, km = m.finish()
+    m.close()
+    assert km == km_want and np.array_equal(got, want)
+    assert int(want.sum()) > 0
+
+
 def test_bound_outputs_accumulate_and_wrap(torch_dev):
     """Counts bound to a caller buffer accumulate modulo 2^32 (uint32 semantics)."""
     import torch

@@ -2,10 +2,10 @@
 # Ablation breakdown of the C2 kernel (k = 21 flank kernel): time per variant
 # (tools/ab.py, one process) and instruction counts per variant (one
 # rocprofv3 --pmc pass over the same variants).  VAFC_ABLATE: 0 full, 4 no hit
-# loop, 1 no LDS filter reads, 5 = 1+4, 2 no read loads, 7 VALU only.
+# loop, 1 no LDS filter reads, 5 = 1+4.
 set -o pipefail
 R=$(pwd); O=$R/gpurun_out; TAG=${TAG:-r04c}
-V="${ABL:-VAFC_ABLATE=0 VAFC_ABLATE=4 VAFC_ABLATE=1 VAFC_ABLATE=5 VAFC_ABLATE=2 VAFC_ABLATE=7}"
+V="${ABL:-VAFC_ABLATE=0 VAFC_ABLATE=4 VAFC_ABLATE=1 VAFC_ABLATE=5}"
 export VAFC_LIB=$R/kmer-cnt_amd/lib_ab/abl/libvafc.so
 timeout -k 10 300 python tools/ab.py --rounds 6 $V > $O/${TAG}_abl_time.log 2>&1 || { echo ABL_TIME_FAILED; tail $O/${TAG}_abl_time.log; exit 1; }
 cat $O/${TAG}_abl_time.log

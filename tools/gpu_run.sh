@@ -14,6 +14,7 @@
 #                                                 ablation: time per VAFC_ABLATE variant of one
 #                                                 library in one process, then one PMC pass of
 #                                                 the same variants        -> TAG_abl_time.log, TAG_abl_pmc/
+#                                                 (VAFC_ABLATE=n, n of 0 1 4 5 64 1024 2048 4096)
 #   tools/gpu_run.sh prof TAG [CONFIGS]           rocprofv3 kernel trace + stats and the PMC passes
 #                                                 of the counting kernel   -> TAG_prof_C/, TAG_pmc_C/
 #   tools/gpu_run.sh profbench TAG [bench args]   rocprofv3 --kernel-trace --stats of one whole
