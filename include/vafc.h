@@ -511,6 +511,73 @@ int vc_corr_write(const vc_vafset *s, const double *corr, const char *path);
 int vc_corr_tree(const vc_vafset *s, const double *corr, const char *path);
 
 /* ------------------------------------------------------------------ */
+/* ed-vaf-counter: approximate pattern search in reads                 */
+/* (ed-vaf-counter.c; its edlibAlign calls in HW mode, EDLIB_TASK_LOC) */
+/* ------------------------------------------------------------------ */
+
+/* A query is a byte string of length m, 1 <= m <= 127; bytes compare exactly
+ * (no case folding, N = N, bytes >= 0x80 are ordinary symbols).  For a read T
+ * of n bytes and a query P let D be the edit-distance table with D[0][j] = 0,
+ * D[i][-1] = i and unit costs, s_j = D[m][j], e' = m if max_edit < 0 else
+ * max_edit, k' = min(e', m).  The hit count of (T, P) is 1 when n = 0;
+ * otherwise the candidates are s_0..s_{n-1}, plus one of value m when k' = m
+ * and n < 64 * ceil(m / 64) - m, and the count is the number of candidates
+ * equal to their minimum b if b <= k', else 0.  This is what the reference
+ * adds per search_kmer_in_seq call (ed-vaf-counter.c:95-119: numLocations of
+ * edlibAlign).  Counts are uint32 sums over all reads and wrap modulo 2^32
+ * (ed-vaf-counter.c:37-38,147-148).  Forward strand only. */
+typedef struct vc_ed vc_ed;
+
+/* The queries of a pattern database (load_patterns, ed-vaf-counter.c:47-83,
+ * and the two searches per pattern, :143-144): pattern i's ref query is the
+ * m = strlen(ref_kmer) bytes of ref_kmer, its alt query the first m bytes of
+ * alt_kmer, padded with NUL bytes when alt_kmer is shorter.  Counts layout
+ * [2 * n_patterns]: ref of pattern i at [2i], alt at [2i + 1].  max_edit is
+ * the CLI's -e.  VC_EINVAL for a length outside 1..127. */
+int vc_ed_create(vc_ed **out, const vc_patterns *db, int max_edit, int device);
+/* The same from arbitrary byte strings: query i is queries[q_offs[i] ..
+ * q_offs[i] + q_lens[i]), counts layout [n_queries]. */
+int vc_ed_create_raw(vc_ed **out, const uint8_t *queries, const uint32_t *q_offs, const uint32_t *q_lens,
+                     size_t n_queries, int max_edit, int device);
+void vc_ed_destroy(vc_ed *ed);
+/* Search one block of host-resident reads (the loop body of count_fastq_kmers,
+ * ed-vaf-counter.c:137-150): staged through pinned memory, asynchronous,
+ * accumulating, buffers reusable on return -- as vc_count_block.  Every read
+ * counts, empty ones included. */
+int vc_ed_count_block(vc_ed *ed, const uint8_t *seq, size_t seq_bytes, const uint64_t *offs, const uint32_t *lens,
+                      uint64_t n_reads);
+/* The same for device-resident reads on `stream` (NULL: HIP's null stream,
+ * VC_STREAM_CTX: the handle's own), with vc_count_device's ordering
+ * contract: after the handle's earlier work, before its later work, no host
+ * synchronisation.  seq_bytes bounds every device read; a read reaching past
+ * it makes vc_ed_finish return VC_EINVAL. */
+int vc_ed_count_device(vc_ed *ed, const uint8_t *d_seq, size_t seq_bytes, const uint64_t *d_offs,
+                       const uint32_t *d_lens, uint64_t n_reads, void *stream);
+/* Wait for all queued work and copy the counts to the host (the counters the
+ * reference sums and writes, ed-vaf-counter.c:204-228). */
+int vc_ed_finish(vc_ed *ed, uint32_t *counts);
+/* Zero the counts (asynchronous on the handle's stream). */
+int vc_ed_reset(vc_ed *ed);
+/* Start the counts from host values instead of zero (asynchronous), e.g. to
+ * continue an earlier run or to check the wrap at 2^32. */
+int vc_ed_set_counts(vc_ed *ed, const uint32_t *counts);
+/* Test and experiment hook: later count calls split a batch into at most
+ * max_ranges read ranges per query block (0, the default: sized from the
+ * device's CU count so that a batch fills it).  Fewer ranges mean more reads
+ * per block; the counts do not depend on it. */
+int vc_ed_set_max_ranges(vc_ed *ed, uint32_t max_ranges);
+/* Elapsed milliseconds of the kernels of the last count call (HIP events
+ * recorded around them on the stream they ran on; synchronises on it). */
+int vc_ed_kernel_ms(vc_ed *ed, float *ms);
+/* count_fastq_kmers (ed-vaf-counter.c:122-154): every record of a FASTA/FASTQ
+ * file, plain or gzip, read with kseq_read semantics until the first negative
+ * return, searched in pinned batches that alternate with the kernel.
+ * n_threads: inflate threads for gzip input.  st (may be NULL): bases and
+ * seqs of all records, blocks = batches.  VC_EIO if the file cannot be
+ * opened (the reference warns and skips it, :129-132). */
+int vc_ed_count_file(vc_ed *ed, const char *path, int n_threads, vc_file_stats *st);
+
+/* ------------------------------------------------------------------ */
 /* Synthetic workload (bench / tests): the generator of vafc_synth.py,  */
 /* evaluated on the device.                                            */
 /* ------------------------------------------------------------------ */

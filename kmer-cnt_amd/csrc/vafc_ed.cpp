@@ -1,0 +1,512 @@
+// vafc_ed.cpp -- host side of the approximate pattern search (vc_ed_* of
+// include/vafc.h): the reference's ed-vaf-counter.c with its edlibAlign calls
+// replaced by the kernels of vafc_ed.hip.
+//
+//   queries       ref / alt k-mers of a pattern database, or raw byte strings
+//   device data   byte -> class map, match masks [group][class][word][lane],
+//                 per-lane query length and output index, one set per word width
+//   count_block   host reads -> pinned staging -> H2D -> kernels (async)
+//   count_file    count_fastq_kmers: kseq records into two alternating batches
+//
+// Nothing here searches on the CPU: any HIP failure is returned as VC_EHIP.
+#include <hip/hip_runtime.h>
+
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <time.h>
+
+#include <new>
+#include <vector>
+
+#include "vafc.h"
+#include "vafc_ed.h"
+#include "vafc_fastq.h"
+
+#define HIPCK(call)                                                                         \
+	do {                                                                                    \
+		hipError_t e_ = (call);                                                             \
+		if (e_ != hipSuccess) {                                                             \
+			fprintf(stderr, "[E::vafc] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_), \
+			        __FILE__, __LINE__);                                                    \
+			return VC_EHIP;                                                                 \
+		}                                                                                   \
+	} while (0)
+
+namespace {
+
+struct EdSlot {
+	uint8_t *h_seq = nullptr;    // pinned
+	uint64_t *h_offs = nullptr;
+	uint32_t *h_lens = nullptr;
+	uint8_t *d_seq = nullptr;
+	uint64_t *d_offs = nullptr;
+	uint32_t *d_lens = nullptr;
+	size_t cap_bytes = 0, cap_reads = 0;
+	hipEvent_t done = nullptr;
+	bool pending = false;
+};
+
+// The queries of one word width, 64 to a group.
+struct EdWidth {
+	uint32_t n_groups = 0;
+	int waves = 1;
+	int lds_masks = 1;
+	void *d_masks = nullptr;
+	uint32_t *d_qlen = nullptr;
+	uint32_t *d_qout = nullptr;
+};
+
+// batches of vc_ed_count_file: bytes and reads per pinned slot
+const size_t ED_BATCH_BYTES = (size_t)8 << 20;
+const size_t ED_BATCH_READS = (size_t)1 << 18;
+
+} // namespace
+
+struct vc_ed {
+	int dev = 0;
+	int max_edit = 0;
+	int n_cu = 256;
+	uint32_t n_out = 0;       // counts
+	uint32_t n_class = 0;
+	hipStream_t st = nullptr;
+	uint8_t *d_cls = nullptr;
+	uint32_t *d_counts = nullptr;
+	uint32_t *d_flags = nullptr;
+	EdWidth width[VC_ED_WIDTHS];
+	EdSlot slot[2];
+	int cur = 0;
+	hipEvent_t t0 = nullptr, t1 = nullptr;
+	bool timed = false;
+	uint32_t max_ranges = 0;   // vc_ed_set_max_ranges: 0 = sized from the device
+	hipEvent_t ev_in = nullptr, ev_out = nullptr;   // vc_ed_count_device on a caller's stream (as vc_count_device)
+};
+
+namespace {
+
+void free_slot(EdSlot &s)
+{
+	if (s.h_seq) (void)hipHostFree(s.h_seq);
+	if (s.h_offs) (void)hipHostFree(s.h_offs);
+	if (s.h_lens) (void)hipHostFree(s.h_lens);
+	if (s.d_seq) (void)hipFree(s.d_seq);
+	if (s.d_offs) (void)hipFree(s.d_offs);
+	if (s.d_lens) (void)hipFree(s.d_lens);
+	s.h_seq = s.d_seq = nullptr;
+	s.h_offs = s.d_offs = nullptr;
+	s.h_lens = s.d_lens = nullptr;
+	s.cap_bytes = s.cap_reads = 0;
+}
+
+// Room for `bytes` and `reads` in a slot; what it already holds (keep_bytes,
+// keep_reads) survives a reallocation.
+int slot_reserve(EdSlot &s, size_t bytes, size_t reads, size_t keep_bytes = 0, size_t keep_reads = 0)
+{
+	if (bytes <= s.cap_bytes && reads <= s.cap_reads) return VC_OK;
+	if (s.pending) HIPCK(hipEventSynchronize(s.done));
+	s.pending = false;
+	const size_t nb = s.cap_bytes >= bytes ? s.cap_bytes : bytes + bytes / 4 + 4096;
+	const size_t nr = s.cap_reads >= reads ? s.cap_reads : reads + reads / 4 + 1024;
+	EdSlot n;
+	if (hipHostMalloc((void **)&n.h_seq, nb, hipHostMallocDefault) != hipSuccess ||
+	    hipHostMalloc((void **)&n.h_offs, nr * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess ||
+	    hipHostMalloc((void **)&n.h_lens, nr * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess ||
+	    hipMalloc((void **)&n.d_seq, nb) != hipSuccess || hipMalloc((void **)&n.d_offs, nr * sizeof(uint64_t)) != hipSuccess ||
+	    hipMalloc((void **)&n.d_lens, nr * sizeof(uint32_t)) != hipSuccess) {
+		fprintf(stderr, "[E::vafc] batch buffers of %zu bytes, %zu reads: %s\n", nb, nr,
+		        hipGetErrorString(hipGetLastError()));
+		free_slot(n);
+		return VC_EHIP;
+	}
+	if (keep_bytes) memcpy(n.h_seq, s.h_seq, keep_bytes);
+	if (keep_reads) {
+		memcpy(n.h_offs, s.h_offs, keep_reads * sizeof(uint64_t));
+		memcpy(n.h_lens, s.h_lens, keep_reads * sizeof(uint32_t));
+	}
+	n.cap_bytes = nb;
+	n.cap_reads = nr;
+	n.done = s.done;
+	free_slot(s);
+	s = n;
+	return VC_OK;
+}
+
+int slot_acquire(vc_ed *c, EdSlot **out)
+{
+	EdSlot &s = c->slot[c->cur];
+	if (s.pending) {
+		HIPCK(hipEventSynchronize(s.done));
+		s.pending = false;
+	}
+	*out = &s;
+	return VC_OK;
+}
+
+// One kernel per word width that has queries, all reads against each.
+int launch(vc_ed *c, const uint8_t *d_seq, size_t seq_bytes, const uint64_t *d_offs, const uint32_t *d_lens,
+           uint64_t n_reads, hipStream_t st)
+{
+	if (n_reads == 0) return VC_OK;
+	HIPCK(hipEventRecord(c->t0, st));
+	for (int w = 0; w < VC_ED_WIDTHS; ++w) {
+		const EdWidth &E = c->width[w];
+		if (E.n_groups == 0) continue;
+		VcEdArgs A;
+		A.seq = d_seq;
+		A.seq_bytes = seq_bytes;
+		A.offs = d_offs;
+		A.lens = d_lens;
+		A.n_reads = n_reads;
+		A.cls = c->d_cls;
+		A.masks = E.d_masks;
+		A.qlen = E.d_qlen;
+		A.qout = E.d_qout;
+		A.n_groups = E.n_groups;
+		A.n_class = c->n_class;
+		A.max_edit = c->max_edit;
+		A.counts = c->d_counts;
+		A.flags = c->d_flags;
+		// query blocks x read ranges: about two rounds of blocks at 32 waves
+		// per CU, so that a two-query panel fills the chip as well
+		const uint64_t gx = (E.n_groups + (uint32_t)E.waves - 1) / (uint32_t)E.waves;
+		const uint64_t target = (uint64_t)c->n_cu * (32u / (uint32_t)E.waves) * 2;
+		uint64_t gy = (target + gx - 1) / gx;
+		if (c->max_ranges && gy > c->max_ranges) gy = c->max_ranges;
+		if (gy > n_reads) gy = n_reads;
+		if (gy > 65535) gy = 65535;
+		if (gy < 1) gy = 1;
+		A.reads_per_range = (n_reads + gy - 1) / gy;
+		gy = (n_reads + A.reads_per_range - 1) / A.reads_per_range;
+		HIPCK(vc_ed_launch(&A, w, E.waves, E.lds_masks, (unsigned)gx, (unsigned)gy, st));
+	}
+	HIPCK(hipEventRecord(c->t1, st));
+	c->timed = true;
+	return VC_OK;
+}
+
+int slot_submit(vc_ed *c, EdSlot &s, size_t bytes, uint64_t n_reads)
+{
+	if (n_reads) {
+		if (bytes) HIPCK(hipMemcpyAsync(s.d_seq, s.h_seq, bytes, hipMemcpyHostToDevice, c->st));
+		HIPCK(hipMemcpyAsync(s.d_offs, s.h_offs, n_reads * sizeof(uint64_t), hipMemcpyHostToDevice, c->st));
+		HIPCK(hipMemcpyAsync(s.d_lens, s.h_lens, n_reads * sizeof(uint32_t), hipMemcpyHostToDevice, c->st));
+		const int rc = launch(c, s.d_seq, bytes, s.d_offs, s.d_lens, n_reads, c->st);
+		if (rc != VC_OK) return rc;
+		HIPCK(hipEventRecord(s.done, c->st));
+		s.pending = true;
+	}
+	c->cur ^= 1;
+	return VC_OK;
+}
+
+template <typename W> void set_bit(std::vector<uint8_t> &tab, size_t word, unsigned bit)
+{
+	reinterpret_cast<W *>(tab.data())[word] |= (W)1 << bit;
+}
+
+// Build the device data of a handle.  q: the query bytes, query i at
+// offs[i] of length lens[i] (1..127), its count at out[i].
+int ed_build(vc_ed **outp, const uint8_t *q, const uint32_t *offs, const uint32_t *lens, const uint32_t *out,
+             size_t n, uint32_t n_out, int max_edit, int device)
+{
+	for (size_t i = 0; i < n; ++i)
+		if (lens[i] < 1 || lens[i] > 127) return VC_EINVAL;
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VC_ENODEV;
+	if (device < 0 || device >= ndev) return VC_EINVAL;
+	HIPCK(hipSetDevice(device));
+	vc_ed *c = new (std::nothrow) vc_ed;
+	if (!c) return VC_ENOMEM;
+	c->dev = device;
+	c->max_edit = max_edit;
+	c->n_out = n_out;
+	hipDeviceProp_t prop;
+	if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
+		c->n_cu = prop.multiProcessorCount;
+
+	// symbol classes: one per byte value that occurs in a query, and class 0
+	// for every other byte (no bit of any mask set); with all 256 values in
+	// use there is no other byte and class = byte
+	bool used[256] = {false};
+	for (size_t i = 0; i < n; ++i)
+		for (uint32_t j = 0; j < lens[i]; ++j) used[q[offs[i] + j]] = true;
+	int n_used = 0;
+	for (int b = 0; b < 256; ++b) n_used += used[b] ? 1 : 0;
+	uint8_t cls[256];
+	if (n_used == 256) {
+		for (int b = 0; b < 256; ++b) cls[b] = (uint8_t)b;
+		c->n_class = 256;
+	} else {
+		int next = 1;
+		for (int b = 0; b < 256; ++b) cls[b] = used[b] ? (uint8_t)next++ : (uint8_t)0;
+		c->n_class = (uint32_t)next;
+	}
+
+#define TRY(call)                                                                                  \
+	do {                                                                                           \
+		hipError_t e_ = (call);                                                                    \
+		if (e_ != hipSuccess) {                                                                    \
+			fprintf(stderr, "[E::vafc] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_),     \
+			        __FILE__, __LINE__);                                                           \
+			vc_ed_destroy(c);                                                                      \
+			return VC_EHIP;                                                                        \
+		}                                                                                          \
+	} while (0)
+	TRY(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
+	TRY(hipMalloc((void **)&c->d_cls, 256));
+	TRY(hipMemcpy(c->d_cls, cls, 256, hipMemcpyHostToDevice));
+	TRY(hipMalloc((void **)&c->d_counts, ((size_t)n_out + 2) * sizeof(uint32_t)));
+	TRY(hipMemset(c->d_counts, 0, ((size_t)n_out + 2) * sizeof(uint32_t)));
+	TRY(hipMalloc((void **)&c->d_flags, sizeof(uint32_t)));
+	TRY(hipMemset(c->d_flags, 0, sizeof(uint32_t)));
+	TRY(hipEventCreate(&c->t0));
+	TRY(hipEventCreate(&c->t1));
+	for (EdSlot &s : c->slot) TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+
+	for (int w = 0; w < VC_ED_WIDTHS; ++w) {
+		const uint32_t lo = w == VC_ED_W32 ? 1 : (w == VC_ED_W64 ? 33 : 65);
+		const uint32_t hi = w == VC_ED_W32 ? 32 : (w == VC_ED_W64 ? 64 : 127);
+		std::vector<size_t> ids;
+		for (size_t i = 0; i < n; ++i)
+			if (lens[i] >= lo && lens[i] <= hi) ids.push_back(i);
+		if (ids.empty()) continue;
+		EdWidth &E = c->width[w];
+		const int nwords = vc_ed_width_words(w), wb = vc_ed_width_wordbytes(w);
+		const unsigned bits = (unsigned)wb * 8;
+		E.n_groups = (uint32_t)((ids.size() + 63) / 64);
+		E.waves = E.n_groups < VC_ED_MAX_WAVES ? (int)E.n_groups : VC_ED_MAX_WAVES;
+		E.lds_masks = (size_t)c->n_class * nwords * E.waves * 64 * wb <= VC_ED_LDS_MASKS ? 1 : 0;
+		const size_t lanes = (size_t)E.n_groups * 64;
+		const size_t words = lanes * c->n_class * nwords;
+		std::vector<uint8_t> tab(words * wb, 0);
+		std::vector<uint32_t> qlen(lanes, 0), qout(lanes, 0);
+		for (size_t s = 0; s < ids.size(); ++s) {
+			const size_t i = ids[s], g = s / 64, lane = s % 64;
+			qlen[s] = lens[i];
+			qout[s] = out[i];
+			for (uint32_t j = 0; j < lens[i]; ++j) {
+				const unsigned cl = cls[q[offs[i] + j]];
+				const size_t word = ((g * c->n_class + cl) * nwords + j / bits) * 64 + lane;
+				if (wb == 4) set_bit<uint32_t>(tab, word, j % bits);
+				else set_bit<uint64_t>(tab, word, j % bits);
+			}
+		}
+		TRY(hipMalloc(&E.d_masks, tab.size()));
+		TRY(hipMemcpy(E.d_masks, tab.data(), tab.size(), hipMemcpyHostToDevice));
+		TRY(hipMalloc((void **)&E.d_qlen, lanes * sizeof(uint32_t)));
+		TRY(hipMemcpy(E.d_qlen, qlen.data(), lanes * sizeof(uint32_t), hipMemcpyHostToDevice));
+		TRY(hipMalloc((void **)&E.d_qout, lanes * sizeof(uint32_t)));
+		TRY(hipMemcpy(E.d_qout, qout.data(), lanes * sizeof(uint32_t), hipMemcpyHostToDevice));
+	}
+#undef TRY
+	*outp = c;
+	return VC_OK;
+}
+
+double now_s()
+{
+	struct timespec ts;
+	clock_gettime(CLOCK_MONOTONIC, &ts);
+	return ts.tv_sec + ts.tv_nsec * 1e-9;
+}
+
+} // namespace
+
+extern "C" int vc_ed_create_raw(vc_ed **out, const uint8_t *queries, const uint32_t *q_offs, const uint32_t *q_lens,
+                                size_t n_queries, int max_edit, int device)
+{
+	if (!out || (n_queries && (!queries || !q_offs || !q_lens)) || n_queries > 0x7FFFFFFFu) return VC_EINVAL;
+	*out = nullptr;
+	std::vector<uint32_t> idx(n_queries);
+	for (size_t i = 0; i < n_queries; ++i) idx[i] = (uint32_t)i;
+	return ed_build(out, queries, q_offs, q_lens, idx.data(), n_queries, (uint32_t)n_queries, max_edit, device);
+}
+
+extern "C" int vc_ed_create(vc_ed **out, const vc_patterns *db, int max_edit, int device)
+{
+	if (!out || !db) return VC_EINVAL;
+	*out = nullptr;
+	const int n = vc_patterns_count(db);
+	if (n > (0x7FFFFFFF >> 1)) return VC_ETOOMANY;
+	std::vector<uint8_t> q;
+	std::vector<uint32_t> offs, lens, idx;
+	for (int i = 0; i < n; ++i) {
+		const char *rk = nullptr, *ak = nullptr;
+		if (vc_pattern_fields(db, i, nullptr, nullptr, nullptr, nullptr, nullptr, &rk, &ak) != VC_OK) return VC_EINVAL;
+		// kmer_len = strlen(ref_kmer) serves both searches (ed-vaf-counter.c:77,143-144)
+		const size_t m = strlen(rk), ma = strnlen(ak, m);
+		for (int allele = 0; allele < 2; ++allele) {
+			offs.push_back((uint32_t)q.size());
+			lens.push_back((uint32_t)m);
+			idx.push_back(2u * (uint32_t)i + (uint32_t)allele);
+			if (allele == 0) {
+				q.insert(q.end(), rk, rk + m);
+			} else {
+				q.insert(q.end(), ak, ak + ma);
+				q.insert(q.end(), m - ma, (uint8_t)0);   // a shorter alt_kmer is padded with NUL bytes
+			}
+		}
+	}
+	return ed_build(out, q.data(), offs.data(), lens.data(), idx.data(), lens.size(), 2u * (uint32_t)n, max_edit,
+	                device);
+}
+
+extern "C" void vc_ed_destroy(vc_ed *c)
+{
+	if (!c) return;
+	(void)hipSetDevice(c->dev);
+	if (c->st) (void)hipStreamSynchronize(c->st);
+	for (EdSlot &s : c->slot) {
+		free_slot(s);
+		if (s.done) (void)hipEventDestroy(s.done);
+	}
+	for (EdWidth &E : c->width) {
+		if (E.d_masks) (void)hipFree(E.d_masks);
+		if (E.d_qlen) (void)hipFree(E.d_qlen);
+		if (E.d_qout) (void)hipFree(E.d_qout);
+	}
+	if (c->d_cls) (void)hipFree(c->d_cls);
+	if (c->d_counts) (void)hipFree(c->d_counts);
+	if (c->d_flags) (void)hipFree(c->d_flags);
+	if (c->t0) (void)hipEventDestroy(c->t0);
+	if (c->t1) (void)hipEventDestroy(c->t1);
+	if (c->ev_in) (void)hipEventDestroy(c->ev_in);
+	if (c->ev_out) (void)hipEventDestroy(c->ev_out);
+	if (c->st) (void)hipStreamDestroy(c->st);
+	delete c;
+}
+
+extern "C" int vc_ed_count_block(vc_ed *c, const uint8_t *seq, size_t seq_bytes, const uint64_t *offs,
+                                 const uint32_t *lens, uint64_t n_reads)
+{
+	if (!c || (n_reads && (!offs || !lens)) || (seq_bytes && !seq)) return VC_EINVAL;
+	if (n_reads == 0) return VC_OK;
+	for (uint64_t i = 0; i < n_reads; ++i)
+		if (offs[i] > seq_bytes || lens[i] > seq_bytes - offs[i]) return VC_EINVAL;
+	HIPCK(hipSetDevice(c->dev));
+	EdSlot *s;
+	int rc = slot_acquire(c, &s);
+	if (rc == VC_OK) rc = slot_reserve(*s, seq_bytes, n_reads);
+	if (rc != VC_OK) return rc;
+	if (seq_bytes) memcpy(s->h_seq, seq, seq_bytes);
+	memcpy(s->h_offs, offs, n_reads * sizeof(uint64_t));
+	memcpy(s->h_lens, lens, n_reads * sizeof(uint32_t));
+	return slot_submit(c, *s, seq_bytes, n_reads);
+}
+
+extern "C" int vc_ed_count_device(vc_ed *c, const uint8_t *d_seq, size_t seq_bytes, const uint64_t *d_offs,
+                                  const uint32_t *d_lens, uint64_t n_reads, void *stream)
+{
+	if (!c || (n_reads && (!d_offs || !d_lens)) || (seq_bytes && !d_seq)) return VC_EINVAL;
+	if (n_reads == 0) return VC_OK;
+	HIPCK(hipSetDevice(c->dev));
+	const hipStream_t st = stream == VC_STREAM_CTX ? c->st : (hipStream_t)stream;
+	if (st == c->st) return launch(c, d_seq, seq_bytes, d_offs, d_lens, n_reads, st);
+	if (!c->ev_in) HIPCK(hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
+	if (!c->ev_out) HIPCK(hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming));
+	HIPCK(hipEventRecord(c->ev_in, c->st));           // e.g. a vc_ed_reset before this call
+	HIPCK(hipStreamWaitEvent(st, c->ev_in, 0));
+	const int rc = launch(c, d_seq, seq_bytes, d_offs, d_lens, n_reads, st);
+	if (rc != VC_OK) return rc;
+	HIPCK(hipEventRecord(c->ev_out, st));
+	HIPCK(hipStreamWaitEvent(c->st, c->ev_out, 0));   // vc_ed_finish waits on c->st only
+	return VC_OK;
+}
+
+extern "C" int vc_ed_finish(vc_ed *c, uint32_t *counts)
+{
+	if (!c) return VC_EINVAL;
+	HIPCK(hipSetDevice(c->dev));
+	HIPCK(hipStreamSynchronize(c->st));
+	for (EdSlot &s : c->slot) s.pending = false;
+	uint32_t f = 0;
+	HIPCK(hipMemcpy(&f, c->d_flags, sizeof f, hipMemcpyDeviceToHost));
+	if (f & 1u) {
+		fprintf(stderr, "[E::vafc] a device read reaches past seq_bytes: counts incomplete\n");
+		return VC_EINVAL;
+	}
+	if (counts && c->n_out)
+		HIPCK(hipMemcpy(counts, c->d_counts, (size_t)c->n_out * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	return VC_OK;
+}
+
+extern "C" int vc_ed_reset(vc_ed *c)
+{
+	if (!c) return VC_EINVAL;
+	HIPCK(hipSetDevice(c->dev));
+	HIPCK(hipMemsetAsync(c->d_counts, 0, ((size_t)c->n_out + 2) * sizeof(uint32_t), c->st));
+	HIPCK(hipMemsetAsync(c->d_flags, 0, sizeof(uint32_t), c->st));
+	return VC_OK;
+}
+
+extern "C" int vc_ed_set_counts(vc_ed *c, const uint32_t *counts)
+{
+	if (!c || (c->n_out && !counts)) return VC_EINVAL;
+	HIPCK(hipSetDevice(c->dev));
+	if (c->n_out) {
+		// pageable source: the copy has left the caller's buffer on return
+		HIPCK(hipMemcpyAsync(c->d_counts, counts, (size_t)c->n_out * sizeof(uint32_t), hipMemcpyHostToDevice, c->st));
+		HIPCK(hipStreamSynchronize(c->st));
+	}
+	return VC_OK;
+}
+
+extern "C" int vc_ed_set_max_ranges(vc_ed *c, uint32_t max_ranges)
+{
+	if (!c) return VC_EINVAL;
+	c->max_ranges = max_ranges;
+	return VC_OK;
+}
+
+extern "C" int vc_ed_kernel_ms(vc_ed *c, float *ms)
+{
+	if (!c || !ms || !c->timed) return VC_EINVAL;
+	HIPCK(hipEventSynchronize(c->t1));
+	HIPCK(hipEventElapsedTime(ms, c->t0, c->t1));
+	return VC_OK;
+}
+
+extern "C" int vc_ed_count_file(vc_ed *c, const char *path, int n_threads, vc_file_stats *stats)
+{
+	if (!c || !path) return VC_EINVAL;
+	const double t0 = now_s();
+	vc_file_stats st;
+	memset(&st, 0, sizeof st);
+	VcFastqReader rd;
+	if (!(n_threads > 1 ? rd.open_parallel(path, n_threads) : rd.open(path))) return VC_EIO;
+	HIPCK(hipSetDevice(c->dev));
+	EdSlot *s = nullptr;
+	size_t bytes = 0, reads = 0;
+	int rc = slot_acquire(c, &s);
+	if (rc == VC_OK) rc = slot_reserve(*s, ED_BATCH_BYTES, ED_BATCH_READS);
+	// a record that returns < 0 ends the file (ed-vaf-counter.c:137)
+	while (rc == VC_OK) {
+		const int ret = rd.next();
+		if (ret < 0) break;
+		const size_t len = rd.seq_len();
+		if (reads && (bytes + len > ED_BATCH_BYTES || reads >= ED_BATCH_READS)) {
+			rc = slot_submit(c, *s, bytes, reads);
+			++st.blocks;
+			bytes = reads = 0;
+			if (rc == VC_OK) rc = slot_acquire(c, &s);
+			if (rc == VC_OK) rc = slot_reserve(*s, ED_BATCH_BYTES, ED_BATCH_READS);
+			if (rc != VC_OK) break;
+		}
+		rc = slot_reserve(*s, bytes + len, reads + 1, bytes, reads);   // a read longer than a batch
+		if (rc != VC_OK) break;
+		if (len) memcpy(s->h_seq + bytes, rd.seq(), len);
+		s->h_offs[reads] = bytes;
+		s->h_lens[reads] = (uint32_t)len;
+		bytes += len;
+		++reads;
+		st.bases += len;
+		++st.seqs;
+	}
+	if (rc == VC_OK && reads) {
+		rc = slot_submit(c, *s, bytes, reads);
+		++st.blocks;
+	}
+	st.seconds = now_s() - t0;
+	if (stats) *stats = st;
+	return rc;
+}

@@ -52,6 +52,8 @@ EXPORTS = (
     "vc_vafset_create", "vc_vafset_free", "vc_vafset_add", "vc_vafset_add_many", "vc_vafset_add_arrays",
     "vc_vafset_count",
     "vc_vafset_name", "vc_vafset_snps", "vc_corr_matrix", "vc_corr_matrix_raw", "vc_corr_write", "vc_corr_tree",
+    "vc_ed_create", "vc_ed_create_raw", "vc_ed_destroy", "vc_ed_count_block", "vc_ed_count_device",
+    "vc_ed_finish", "vc_ed_reset", "vc_ed_set_counts", "vc_ed_set_max_ranges", "vc_ed_kernel_ms", "vc_ed_count_file",
     "vc_synth_reads",
     "vc_debug_decode", "vc_strerror", "vc_version", "vc_build_id",
 )
@@ -209,6 +211,17 @@ def lib():
                                          C.POINTER(C.c_float)]),
         "vc_corr_write": (C.c_int, [P, P, C.c_char_p]),
         "vc_corr_tree": (C.c_int, [P, P, C.c_char_p]),
+        "vc_ed_create": (C.c_int, [C.POINTER(P), P, C.c_int, C.c_int]),
+        "vc_ed_create_raw": (C.c_int, [C.POINTER(P), P, P, P, C.c_size_t, C.c_int, C.c_int]),
+        "vc_ed_destroy": (None, [P]),
+        "vc_ed_count_block": (C.c_int, [P, P, C.c_size_t, P, P, C.c_uint64]),
+        "vc_ed_count_device": (C.c_int, [P, P, C.c_size_t, P, P, C.c_uint64, P]),
+        "vc_ed_finish": (C.c_int, [P, P]),
+        "vc_ed_reset": (C.c_int, [P]),
+        "vc_ed_set_counts": (C.c_int, [P, P]),
+        "vc_ed_set_max_ranges": (C.c_int, [P, C.c_uint32]),
+        "vc_ed_kernel_ms": (C.c_int, [P, C.POINTER(C.c_float)]),
+        "vc_ed_count_file": (C.c_int, [P, C.c_char_p, C.c_int, C.POINTER(FileStats)]),
         "vc_synth_reads": (C.c_int, [P, P, P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64,
                                      C.c_double, P, P, C.c_uint32, P]),
         "vc_debug_decode": (C.c_int, [P, C.c_size_t, P, P, C.c_uint64, P, P]),
@@ -269,7 +282,8 @@ def check_build(paths=None) -> None:
                             want, ", ".join("%s has %s" % (n, i) for n, i in bad)))
 
 
-BINARIES = ("libvafc.so", "vaf-counter", "snp-pattern-gen", "kc-c4", "yak-count", "correlation-matrix")
+BINARIES = ("libvafc.so", "vaf-counter", "snp-pattern-gen", "kc-c4", "yak-count", "correlation-matrix",
+            "ed-vaf-counter")
 
 
 def _ck(rc, what):
@@ -1224,3 +1238,150 @@ def correlation_matrix_raw(vaf: np.ndarray, depth: np.ndarray, n_snps=None, min_
     _ck(lib().vc_corr_matrix_raw(_ptr(vaf), _ptr(depth), _ptr(ns), n, stride, min_snps, min_depth, _ptr(corr),
                                  device, C.byref(ms)), "vc_corr_matrix_raw")
     return corr, ms.value
+
+
+# ---------------------------------------------------------------------------
+# ed-vaf-counter: approximate pattern search in reads (ed-vaf-counter.c), the
+# names of the reference's functions over vc_ed_* in libvafc.so
+# ---------------------------------------------------------------------------
+
+class EdCounter:
+    """Every query against every read with a bounded edit distance on the GPU
+    (search_kmer_in_seq over all patterns, ed-vaf-counter.c:95-150; the count
+    rule is stated in include/vafc.h).  From a PatternDB the counts are
+    uint32[2 * n_patterns] (ref, alt interleaved); from ``queries`` (a list of
+    byte strings of 1..127 bytes) they are uint32[len(queries)]."""
+
+    def __init__(self, db: PatternDB = None, max_edit: int = 0, device: int = 0, queries=None):
+        h = P()
+        if queries is not None:
+            qs = [bytes(q) for q in queries]
+            lens = np.array([len(q) for q in qs], np.uint32)
+            offs = (np.cumsum(lens, dtype=np.uint64) - lens).astype(np.uint32)
+            blob = np.frombuffer(b"".join(qs) + b"\0", np.uint8)
+            _ck(lib().vc_ed_create_raw(C.byref(h), _ptr(blob), _ptr(offs), _ptr(lens), len(qs), max_edit, device),
+                "vc_ed_create_raw")
+            self.n_counts = len(qs)
+        else:
+            _ck(lib().vc_ed_create(C.byref(h), db._h, max_edit, device), "vc_ed_create")
+            self.n_counts = 2 * db.n
+        self._h = h
+        self.max_edit, self.device = max_edit, device
+
+    def count_block(self, seq: np.ndarray, offs: np.ndarray, lens: np.ndarray) -> None:
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        assert offs.size == lens.size
+        _ck(lib().vc_ed_count_block(self._h, _ptr(seq) if seq.size else None, seq.size, _ptr(offs), _ptr(lens),
+                                    offs.size), "vc_ed_count_block")
+
+    def count_device(self, seq_ptr: int, seq_bytes: int, offs_ptr: int, lens_ptr: int, n_reads: int,
+                     stream: int = 0) -> None:
+        """HBM-resident reads on `stream` (as KmerMap.count_device)."""
+        _ck(lib().vc_ed_count_device(self._h, P(seq_ptr) if seq_ptr else None, seq_bytes, P(offs_ptr), P(lens_ptr),
+                                     n_reads, P(stream) if stream else None), "vc_ed_count_device")
+
+    def count_file(self, fn: str, n_thread: int = 4) -> FileStats:
+        """count_fastq_kmers (ed-vaf-counter.c:122-154); FileNotFoundError if
+        the file cannot be opened (the reference warns and goes on)."""
+        st = FileStats()
+        rc = lib().vc_ed_count_file(self._h, fn.encode(), n_thread, C.byref(st))
+        if rc == VC_EIO:
+            raise FileNotFoundError(fn)
+        _ck(rc, "vc_ed_count_file(%s)" % fn)
+        return st
+
+    def finish(self) -> np.ndarray:
+        counts = np.zeros(self.n_counts + 2, dtype=np.uint32)
+        _ck(lib().vc_ed_finish(self._h, _ptr(counts)), "vc_ed_finish")
+        return counts[:self.n_counts]
+
+    def reset(self) -> None:
+        _ck(lib().vc_ed_reset(self._h), "vc_ed_reset")
+
+    def set_counts(self, counts: np.ndarray) -> None:
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        assert counts.size >= self.n_counts
+        _ck(lib().vc_ed_set_counts(self._h, _ptr(counts)), "vc_ed_set_counts")
+
+    def set_max_ranges(self, n: int) -> None:
+        """At most n read ranges per query block in later count calls (0: sized
+        from the device); a test hook, the counts do not depend on it."""
+        _ck(lib().vc_ed_set_max_ranges(self._h, n), "vc_ed_set_max_ranges")
+
+    def kernel_ms(self) -> float:
+        ms = C.c_float()
+        _ck(lib().vc_ed_kernel_ms(self._h, C.byref(ms)), "vc_ed_kernel_ms")
+        return ms.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().vc_ed_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ketopt_scan(argv, ostr: str):
+    """ketopt(permute=1, ostr, no long options) over argv (without argv[0]),
+    the scanner of csrc/vafc_opt.h: ([(option, argument or None)], files).
+    An unknown letter or a "--word" is '?', a missing argument ':'."""
+    opts, files, i = [], [], 0
+    while i < len(argv):
+        a = argv[i]
+        if len(a) < 2 or a[0] != "-":
+            files.append(a)
+            i += 1
+            continue
+        if a[1] == "-":
+            if len(a) == 2:
+                files.extend(argv[i + 1:])
+                break
+            opts.append(("?", None))
+            i += 1
+            continue
+        j = 1
+        while j < len(a):
+            c = a[j]
+            j += 1
+            k = ostr.find(c)
+            if k < 0:
+                opts.append(("?", None))
+            elif ostr[k + 1:k + 2] == ":":
+                if j < len(a):
+                    opts.append((c, a[j:]))
+                elif i + 1 < len(argv):
+                    i += 1
+                    opts.append((c, argv[i]))
+                else:
+                    opts.append((":", None))
+                break
+            else:
+                opts.append((c, None))
+        i += 1
+    return opts, files
+
+
+def c_atoi(s: str) -> int:
+    """atoi: optional white space and sign, then digits; 0 without digits."""
+    import re
+    m = re.match(r"[ \t\n\v\f\r]*([+-]?[0-9]+)", s)
+    v = int(m.group(1)) if m else 0
+    return max(-(1 << 31), min((1 << 31) - 1, v))
+
+
+def ed_parse_args(argv):
+    """main's option loop (ed-vaf-counter.c:167-171): ({p, o, e}, files)."""
+    opt = {"p": None, "o": None, "e": 0}
+    opts, files = ketopt_scan(argv, "p:o:e:")
+    for c, a in opts:
+        if c in ("p", "o"):
+            opt[c] = a
+        elif c == "e":
+            opt["e"] = c_atoi(a)
+    return opt, files
