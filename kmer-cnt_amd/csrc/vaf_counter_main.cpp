@@ -16,7 +16,7 @@
 
 #include "vafc.h"
 
-static double now_s()
+static double wall_s()
 {
 	struct timespec ts;
 	clock_gettime(CLOCK_REALTIME, &ts);
@@ -72,20 +72,20 @@ int main(int argc, char *argv[])
 		if (!v.empty()) devices = v;
 	}
 
-	const double t_start = now_s();
+	const double t_start = wall_s();
 	fprintf(stderr, "[M::%s] Loading patterns...\n", "main");
-	double t = now_s();
+	double t = wall_s();
 	vc_patterns *db = nullptr;
 	if (vc_patterns_load(pattern_fn, &db) != VC_OK) {
 		fprintf(stderr, "Error: failed to load pattern file\n");
 		return 1;
 	}
-	const double t_load = now_s() - t;
+	const double t_load = wall_s() - t;
 	const int n = vc_patterns_count(db);
 	fprintf(stderr, "[M::%s] Loaded %d patterns in %.3f sec\n", "main", n, t_load);
 
 	fprintf(stderr, "[M::%s] Creating k-mer map...\n", "main");
-	t = now_s();
+	t = wall_s();
 	uint64_t *keys = nullptr;
 	uint32_t *vals = nullptr;
 	size_t n_keys = 0;
@@ -111,20 +111,20 @@ int main(int argc, char *argv[])
 		vc_patterns_free(db);
 		return 1;
 	}
-	const double t_map = now_s() - t;
+	const double t_map = wall_s() - t;
 	uint64_t tk = 0, tslots = 0, fbytes = 0;
 	vc_table_info(ctx, &tk, &tslots, &fbytes);
 	if (verbose)
 		fprintf(stderr, "[V::%s] Created k-mer map with %d entries in %.3f sec\n", "main", (int)tk, t_map);
 
 	fprintf(stderr, "[M::%s] Counting k-mers in FASTQ files with %d threads...\n", "main", n_thread);
-	t = now_s();
+	t = wall_s();
 	// the reader's pinned buffers are allocated inside the counting timer, as
 	// the reference allocates its per-block buffers inside it (vaf-counter.c:489-503):
 	// by vc_count_file's workers, each slot on its first use, overlapping the
 	// other workers' parsing (VAFC_RESERVE=1: all of them up front, as before)
 	rc = getenv("VAFC_RESERVE") && getenv("VAFC_RESERVE")[0] == '1' ? vc_reserve_file_ingest(ctx, n_thread) : VC_OK;
-	const double t_reserved = now_s();
+	const double t_reserved = wall_s();
 	if (rc != VC_OK) {
 		fprintf(stderr, "Error: counting failed (%s)\n", vc_strerror(rc));
 		vc_destroy(ctx);
@@ -152,9 +152,9 @@ int main(int argc, char *argv[])
 	}
 	std::vector<uint32_t> counts(2 * (size_t)n + 2, 0);
 	uint64_t kmers = 0;
-	const double t_read = now_s();
+	const double t_read = wall_s();
 	rc = vc_finish(ctx, counts.data(), &kmers);
-	const double t_count = now_s() - t;
+	const double t_count = wall_s() - t;
 	// VAFC_PHASES=1: the counting timer split into the reader's buffer
 	// allocation (pinned slots of every shard), the reading and counting of
 	// the files, and vc_finish (the last batches, the shard sum / RCCL reduce
@@ -162,7 +162,7 @@ int main(int argc, char *argv[])
 	if (getenv("VAFC_PHASES"))
 		fprintf(stderr, "[P::main] shards %d threads %d: reserve %.4f s, read+count %.4f s, finish %.4f s, "
 		        "counting %.4f s\n", (int)devices.size(), n_thread, t_reserved - t, t_read - t_reserved,
-		        now_s() - t_read, t_count);
+		        wall_s() - t_read, t_count);
 	if (rc != VC_OK) {
 		fprintf(stderr, "Error: counting failed (%s)\n", vc_strerror(rc));
 		vc_destroy(ctx);
@@ -177,18 +177,18 @@ int main(int argc, char *argv[])
 	const double avg = (double)(tot_ref + tot_alt) / (n > 0 ? n : 1);
 
 	fprintf(stderr, "[M::%s] Writing VAF file...\n", "main");
-	t = now_s();
+	t = wall_s();
 	if (vc_write_vaf(db, counts.data(), out_fn) != VC_OK) {
 		fprintf(stderr, "Error: failed to open output file\n");
 		vc_destroy(ctx);
 		vc_patterns_free(db);
 		return 1;
 	}
-	const double t_write = now_s() - t;
+	const double t_write = wall_s() - t;
 	fprintf(stderr, "[M::%s] Done. Average depth: %.2f\n", "main", avg);
 
 	if (verbose) {
-		const double total = now_s() - t_start;
+		const double total = wall_s() - t_start;
 		// the reference reports its khashl geometry: 3n rounded up to a power of two
 		unsigned want = (unsigned)n * 3u, bits = 0, x = want;
 		while ((x >>= 1) != 0) ++bits;

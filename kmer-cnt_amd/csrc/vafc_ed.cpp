@@ -8,13 +8,16 @@
 //   count_block   host reads -> pinned staging -> H2D -> kernels (async)
 //   count_file    count_fastq_kmers: kseq records into two alternating batches
 //
+// The staging (slots, the two-slot stager, the batch writer, the bridge to a
+// caller's stream) is vafc_stage.h, shared with the k-mer counter; only the
+// launch is this file's own.
+//
 // Nothing here searches on the CPU: any HIP failure is returned as VC_EHIP.
 #include <hip/hip_runtime.h>
 
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 #include <new>
 #include <vector>
@@ -22,30 +25,9 @@
 #include "vafc.h"
 #include "vafc_ed.h"
 #include "vafc_fastq.h"
-
-#define HIPCK(call)                                                                         \
-	do {                                                                                    \
-		hipError_t e_ = (call);                                                             \
-		if (e_ != hipSuccess) {                                                             \
-			fprintf(stderr, "[E::vafc] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_), \
-			        __FILE__, __LINE__);                                                    \
-			return VC_EHIP;                                                                 \
-		}                                                                                   \
-	} while (0)
+#include "vafc_stage.h"
 
 namespace {
-
-struct EdSlot {
-	uint8_t *h_seq = nullptr;    // pinned
-	uint64_t *h_offs = nullptr;
-	uint32_t *h_lens = nullptr;
-	uint8_t *d_seq = nullptr;
-	uint64_t *d_offs = nullptr;
-	uint32_t *d_lens = nullptr;
-	size_t cap_bytes = 0, cap_reads = 0;
-	hipEvent_t done = nullptr;
-	bool pending = false;
-};
 
 // The queries of one word width, 64 to a group.
 struct EdWidth {
@@ -57,7 +39,7 @@ struct EdWidth {
 	uint32_t *d_qout = nullptr;
 };
 
-// batches of vc_ed_count_file: bytes and reads per pinned slot
+// batches of vc_ed_count_file: bytes ($VAFC_BATCH_BYTES: vc_batch_bytes) and reads per pinned slot
 const size_t ED_BATCH_BYTES = (size_t)8 << 20;
 const size_t ED_BATCH_READS = (size_t)1 << 18;
 
@@ -74,73 +56,16 @@ struct vc_ed {
 	uint32_t *d_counts = nullptr;
 	uint32_t *d_flags = nullptr;
 	EdWidth width[VC_ED_WIDTHS];
-	EdSlot slot[2];
-	int cur = 0;
+	VcStager stage;
 	hipEvent_t t0 = nullptr, t1 = nullptr;
 	bool timed = false;
 	uint32_t max_ranges = 0;   // vc_ed_set_max_ranges: 0 = sized from the device
-	hipEvent_t ev_in = nullptr, ev_out = nullptr;   // vc_ed_count_device on a caller's stream (as vc_count_device)
+	VcStreamBridge bridge;     // vc_ed_count_device on a caller's stream
+
+	int submit(size_t bytes, uint64_t n_reads);   // the acquired slot of `stage`: H2D copies + kernels
 };
 
 namespace {
-
-void free_slot(EdSlot &s)
-{
-	if (s.h_seq) (void)hipHostFree(s.h_seq);
-	if (s.h_offs) (void)hipHostFree(s.h_offs);
-	if (s.h_lens) (void)hipHostFree(s.h_lens);
-	if (s.d_seq) (void)hipFree(s.d_seq);
-	if (s.d_offs) (void)hipFree(s.d_offs);
-	if (s.d_lens) (void)hipFree(s.d_lens);
-	s.h_seq = s.d_seq = nullptr;
-	s.h_offs = s.d_offs = nullptr;
-	s.h_lens = s.d_lens = nullptr;
-	s.cap_bytes = s.cap_reads = 0;
-}
-
-// Room for `bytes` and `reads` in a slot; what it already holds (keep_bytes,
-// keep_reads) survives a reallocation.
-int slot_reserve(EdSlot &s, size_t bytes, size_t reads, size_t keep_bytes = 0, size_t keep_reads = 0)
-{
-	if (bytes <= s.cap_bytes && reads <= s.cap_reads) return VC_OK;
-	if (s.pending) HIPCK(hipEventSynchronize(s.done));
-	s.pending = false;
-	const size_t nb = s.cap_bytes >= bytes ? s.cap_bytes : bytes + bytes / 4 + 4096;
-	const size_t nr = s.cap_reads >= reads ? s.cap_reads : reads + reads / 4 + 1024;
-	EdSlot n;
-	if (hipHostMalloc((void **)&n.h_seq, nb, hipHostMallocDefault) != hipSuccess ||
-	    hipHostMalloc((void **)&n.h_offs, nr * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess ||
-	    hipHostMalloc((void **)&n.h_lens, nr * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess ||
-	    hipMalloc((void **)&n.d_seq, nb) != hipSuccess || hipMalloc((void **)&n.d_offs, nr * sizeof(uint64_t)) != hipSuccess ||
-	    hipMalloc((void **)&n.d_lens, nr * sizeof(uint32_t)) != hipSuccess) {
-		fprintf(stderr, "[E::vafc] batch buffers of %zu bytes, %zu reads: %s\n", nb, nr,
-		        hipGetErrorString(hipGetLastError()));
-		free_slot(n);
-		return VC_EHIP;
-	}
-	if (keep_bytes) memcpy(n.h_seq, s.h_seq, keep_bytes);
-	if (keep_reads) {
-		memcpy(n.h_offs, s.h_offs, keep_reads * sizeof(uint64_t));
-		memcpy(n.h_lens, s.h_lens, keep_reads * sizeof(uint32_t));
-	}
-	n.cap_bytes = nb;
-	n.cap_reads = nr;
-	n.done = s.done;
-	free_slot(s);
-	s = n;
-	return VC_OK;
-}
-
-int slot_acquire(vc_ed *c, EdSlot **out)
-{
-	EdSlot &s = c->slot[c->cur];
-	if (s.pending) {
-		HIPCK(hipEventSynchronize(s.done));
-		s.pending = false;
-	}
-	*out = &s;
-	return VC_OK;
-}
 
 // One kernel per word width that has queries, all reads against each.
 int launch(vc_ed *c, const uint8_t *d_seq, size_t seq_bytes, const uint64_t *d_offs, const uint32_t *d_lens,
@@ -181,21 +106,6 @@ int launch(vc_ed *c, const uint8_t *d_seq, size_t seq_bytes, const uint64_t *d_o
 	}
 	HIPCK(hipEventRecord(c->t1, st));
 	c->timed = true;
-	return VC_OK;
-}
-
-int slot_submit(vc_ed *c, EdSlot &s, size_t bytes, uint64_t n_reads)
-{
-	if (n_reads) {
-		if (bytes) HIPCK(hipMemcpyAsync(s.d_seq, s.h_seq, bytes, hipMemcpyHostToDevice, c->st));
-		HIPCK(hipMemcpyAsync(s.d_offs, s.h_offs, n_reads * sizeof(uint64_t), hipMemcpyHostToDevice, c->st));
-		HIPCK(hipMemcpyAsync(s.d_lens, s.h_lens, n_reads * sizeof(uint32_t), hipMemcpyHostToDevice, c->st));
-		const int rc = launch(c, s.d_seq, bytes, s.d_offs, s.d_lens, n_reads, c->st);
-		if (rc != VC_OK) return rc;
-		HIPCK(hipEventRecord(s.done, c->st));
-		s.pending = true;
-	}
-	c->cur ^= 1;
 	return VC_OK;
 }
 
@@ -261,7 +171,10 @@ int ed_build(vc_ed **outp, const uint8_t *q, const uint32_t *offs, const uint32_
 	TRY(hipMemset(c->d_flags, 0, sizeof(uint32_t)));
 	TRY(hipEventCreate(&c->t0));
 	TRY(hipEventCreate(&c->t1));
-	for (EdSlot &s : c->slot) TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+	if (c->stage.init() != VC_OK) {
+		vc_ed_destroy(c);
+		return VC_EHIP;
+	}
 
 	for (int w = 0; w < VC_ED_WIDTHS; ++w) {
 		const uint32_t lo = w == VC_ED_W32 ? 1 : (w == VC_ED_W64 ? 33 : 65);
@@ -303,14 +216,14 @@ int ed_build(vc_ed **outp, const uint8_t *q, const uint32_t *offs, const uint32_
 	return VC_OK;
 }
 
-double now_s()
-{
-	struct timespec ts;
-	clock_gettime(CLOCK_MONOTONIC, &ts);
-	return ts.tv_sec + ts.tv_nsec * 1e-9;
-}
-
 } // namespace
+
+int vc_ed::submit(size_t bytes, uint64_t n_reads)
+{
+	return stage.submit(bytes, n_reads, st, [&](const VcSlot &s) {
+		return launch(this, s.d_seq, bytes, s.d_offs, s.d_lens, n_reads, st);
+	});
+}
 
 extern "C" int vc_ed_create_raw(vc_ed **out, const uint8_t *queries, const uint32_t *q_offs, const uint32_t *q_lens,
                                 size_t n_queries, int max_edit, int device)
@@ -356,10 +269,7 @@ extern "C" void vc_ed_destroy(vc_ed *c)
 	if (!c) return;
 	(void)hipSetDevice(c->dev);
 	if (c->st) (void)hipStreamSynchronize(c->st);
-	for (EdSlot &s : c->slot) {
-		free_slot(s);
-		if (s.done) (void)hipEventDestroy(s.done);
-	}
+	c->stage.destroy();
 	for (EdWidth &E : c->width) {
 		if (E.d_masks) (void)hipFree(E.d_masks);
 		if (E.d_qlen) (void)hipFree(E.d_qlen);
@@ -370,8 +280,7 @@ extern "C" void vc_ed_destroy(vc_ed *c)
 	if (c->d_flags) (void)hipFree(c->d_flags);
 	if (c->t0) (void)hipEventDestroy(c->t0);
 	if (c->t1) (void)hipEventDestroy(c->t1);
-	if (c->ev_in) (void)hipEventDestroy(c->ev_in);
-	if (c->ev_out) (void)hipEventDestroy(c->ev_out);
+	c->bridge.destroy();
 	if (c->st) (void)hipStreamDestroy(c->st);
 	delete c;
 }
@@ -384,14 +293,14 @@ extern "C" int vc_ed_count_block(vc_ed *c, const uint8_t *seq, size_t seq_bytes,
 	for (uint64_t i = 0; i < n_reads; ++i)
 		if (offs[i] > seq_bytes || lens[i] > seq_bytes - offs[i]) return VC_EINVAL;
 	HIPCK(hipSetDevice(c->dev));
-	EdSlot *s;
-	int rc = slot_acquire(c, &s);
-	if (rc == VC_OK) rc = slot_reserve(*s, seq_bytes, n_reads);
+	VcSlot *s;
+	int rc = c->stage.acquire(&s);
+	if (rc == VC_OK) rc = vc_slot_reserve(*s, seq_bytes, n_reads);
 	if (rc != VC_OK) return rc;
 	if (seq_bytes) memcpy(s->h_seq, seq, seq_bytes);
 	memcpy(s->h_offs, offs, n_reads * sizeof(uint64_t));
 	memcpy(s->h_lens, lens, n_reads * sizeof(uint32_t));
-	return slot_submit(c, *s, seq_bytes, n_reads);
+	return c->submit(seq_bytes, n_reads);
 }
 
 extern "C" int vc_ed_count_device(vc_ed *c, const uint8_t *d_seq, size_t seq_bytes, const uint64_t *d_offs,
@@ -401,16 +310,10 @@ extern "C" int vc_ed_count_device(vc_ed *c, const uint8_t *d_seq, size_t seq_byt
 	if (n_reads == 0) return VC_OK;
 	HIPCK(hipSetDevice(c->dev));
 	const hipStream_t st = stream == VC_STREAM_CTX ? c->st : (hipStream_t)stream;
-	if (st == c->st) return launch(c, d_seq, seq_bytes, d_offs, d_lens, n_reads, st);
-	if (!c->ev_in) HIPCK(hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
-	if (!c->ev_out) HIPCK(hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming));
-	HIPCK(hipEventRecord(c->ev_in, c->st));           // e.g. a vc_ed_reset before this call
-	HIPCK(hipStreamWaitEvent(st, c->ev_in, 0));
-	const int rc = launch(c, d_seq, seq_bytes, d_offs, d_lens, n_reads, st);
-	if (rc != VC_OK) return rc;
-	HIPCK(hipEventRecord(c->ev_out, st));
-	HIPCK(hipStreamWaitEvent(c->st, c->ev_out, 0));   // vc_ed_finish waits on c->st only
-	return VC_OK;
+	int rc = c->bridge.enter(c->st, st);
+	if (rc == VC_OK) rc = launch(c, d_seq, seq_bytes, d_offs, d_lens, n_reads, st);
+	if (rc == VC_OK) rc = c->bridge.leave(c->st, st);
+	return rc;
 }
 
 extern "C" int vc_ed_finish(vc_ed *c, uint32_t *counts)
@@ -418,7 +321,7 @@ extern "C" int vc_ed_finish(vc_ed *c, uint32_t *counts)
 	if (!c) return VC_EINVAL;
 	HIPCK(hipSetDevice(c->dev));
 	HIPCK(hipStreamSynchronize(c->st));
-	for (EdSlot &s : c->slot) s.pending = false;
+	c->stage.settle();
 	uint32_t f = 0;
 	HIPCK(hipMemcpy(&f, c->d_flags, sizeof f, hipMemcpyDeviceToHost));
 	if (f & 1u) {
@@ -469,44 +372,24 @@ extern "C" int vc_ed_kernel_ms(vc_ed *c, float *ms)
 extern "C" int vc_ed_count_file(vc_ed *c, const char *path, int n_threads, vc_file_stats *stats)
 {
 	if (!c || !path) return VC_EINVAL;
-	const double t0 = now_s();
+	const double t0 = vc_now();
 	vc_file_stats st;
 	memset(&st, 0, sizeof st);
 	VcFastqReader rd;
 	if (!(n_threads > 1 ? rd.open_parallel(path, n_threads) : rd.open(path))) return VC_EIO;
 	HIPCK(hipSetDevice(c->dev));
-	EdSlot *s = nullptr;
-	size_t bytes = 0, reads = 0;
-	int rc = slot_acquire(c, &s);
-	if (rc == VC_OK) rc = slot_reserve(*s, ED_BATCH_BYTES, ED_BATCH_READS);
+	VcBatchWriter bw(vc_batch_bytes(ED_BATCH_BYTES), ED_BATCH_READS, [c]() { return c; });
+	int rc = VC_OK;
 	// a record that returns < 0 ends the file (ed-vaf-counter.c:137)
-	while (rc == VC_OK) {
-		const int ret = rd.next();
-		if (ret < 0) break;
+	while (rd.next() >= 0) {
 		const size_t len = rd.seq_len();
-		if (reads && (bytes + len > ED_BATCH_BYTES || reads >= ED_BATCH_READS)) {
-			rc = slot_submit(c, *s, bytes, reads);
-			++st.blocks;
-			bytes = reads = 0;
-			if (rc == VC_OK) rc = slot_acquire(c, &s);
-			if (rc == VC_OK) rc = slot_reserve(*s, ED_BATCH_BYTES, ED_BATCH_READS);
-			if (rc != VC_OK) break;
-		}
-		rc = slot_reserve(*s, bytes + len, reads + 1, bytes, reads);   // a read longer than a batch
-		if (rc != VC_OK) break;
-		if (len) memcpy(s->h_seq + bytes, rd.seq(), len);
-		s->h_offs[reads] = bytes;
-		s->h_lens[reads] = (uint32_t)len;
-		bytes += len;
-		++reads;
+		if ((rc = bw.add(rd.seq(), len)) != VC_OK) break;
 		st.bases += len;
 		++st.seqs;
 	}
-	if (rc == VC_OK && reads) {
-		rc = slot_submit(c, *s, bytes, reads);
-		++st.blocks;
-	}
-	st.seconds = now_s() - t0;
+	if (rc == VC_OK) rc = bw.flush();
+	st.blocks = bw.batches;
+	st.seconds = vc_now() - t0;
 	if (stats) *stats = st;
 	return rc;
 }

@@ -1,6 +1,7 @@
 // vafc_fastq.cpp -- see vafc_fastq.h.
 #include "vafc_fastq.h"
 #include "vafc_gzip.h"
+#include "vafc_ingest.h"
 
 #include <ctype.h>
 #include <stdlib.h>
@@ -96,11 +97,7 @@ bool VcFastqReader::open_parallel(const char *path, int threads, uint64_t chunk_
 {
 	close();
 	if (threads >= 1) {
-		if (!chunk_bytes) {   // 0: sized by the inflater from the file size
-			const char *e = getenv("VAFC_GZ_CHUNK");   // test knob
-			chunk_bytes = e && atoll(e) > 0 ? (uint64_t)atoll(e) : 0;
-		}
-		gzp_ = vc_gzp_open(path, threads, chunk_bytes);
+		gzp_ = vc_gzp_open(path, threads, chunk_bytes ? chunk_bytes : vc_gz_chunk());
 	}
 	if (!gzp_) return open(path, window);
 	cap_ = 0;

@@ -1,12 +1,14 @@
 // vafc_host.cpp -- host side of libvafc.so: the C ABI of include/vafc.h.
 //
-//   patterns      load_patterns / create_combined_kmer_map   vaf-counter.c:149-252
 //   device ctx    static key table + LDS prefilter in HBM, counts, streams
 //   count_block   host block -> pinned staging -> H2D -> kernels (async)
 //   count_file    count_fastq_kmers: block loop + kseq reader  vaf-counter.c:482-582
 //   shards        one table replica + counts per GPU, host batches dealt
 //                 round robin, one RCCL reduce before the writer  
-//   write_vaf     .vaf writer                                  vaf-counter.c:653-681
+//
+// The pattern database and the .vaf writer are vafc_patterns.cpp; the staging
+// of host batches (slots, stager, batch writer, caller-stream bridge) is
+// vafc_stage.h, shared with vafc_ed.cpp.
 //
 // Nothing here computes counts on the CPU: every k-mer goes through the HIP
 // kernels in vafc_kernels.hip, and any HIP failure is returned as VC_EHIP.
@@ -17,7 +19,6 @@
 #include <dlfcn.h>
 #include <sched.h>
 #include <fcntl.h>
-#include <limits.h>
 #include <math.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -27,7 +28,6 @@
 #include <string.h>
 
 #include <mutex>
-#include <unordered_map>
 #include <vector>
 
 #include "vafc.h"
@@ -38,209 +38,11 @@
 #include "vafc_ingest.h"
 #include "vafc_internal.h"
 #include "vafc_kc.h"
-
-#define HIPCK(call)                                                                         \
-	do {                                                                                    \
-		hipError_t e_ = (call);                                                             \
-		if (e_ != hipSuccess) {                                                             \
-			fprintf(stderr, "[E::vafc] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_), \
-			        __FILE__, __LINE__);                                                    \
-			return VC_EHIP;                                                                 \
-		}                                                                                   \
-	} while (0)
-
-// ---------------------------------------------------------------------------
-// patterns
-// ---------------------------------------------------------------------------
-
-namespace {
-
-struct Pattern {
-	char chr[256];
-	int start, end;
-	char rsid[256];
-	char ref, alt;
-	char ref_kmer[128];
-	char alt_kmer[128];
-};
-
-unsigned char g_nt4[256];
-bool g_nt4_init = false;
-
-void init_nt4()
-{
-	if (g_nt4_init) return;
-	for (int i = 0; i < 256; ++i) g_nt4[i] = 4;
-	for (int i = 0; i < 4; ++i) g_nt4[i] = (unsigned char)i;
-	const char *acgt[4] = {"Aa", "Cc", "Gg", "TtUu"};
-	for (int c = 0; c < 4; ++c)
-		for (const char *p = acgt[c]; *p; ++p) g_nt4[(unsigned char)*p] = (unsigned char)c;
-	g_nt4_init = true;
-}
-
-// 2-bit key of the first k characters (vaf-counter.c:117-127); UINT64_MAX if
-// any of them is not A/C/G/T/U (either case) or a raw byte 0..3.
-uint64_t string_key(const char *s, int k)
-{
-	uint64_t x = 0;
-	for (int i = 0; i < k; ++i) {
-		unsigned c = g_nt4[(unsigned char)s[i]];
-		if (c > 3) return UINT64_MAX;
-		x = (x << 2) | c;
-	}
-	return x;
-}
-
-uint64_t canonical(uint64_t x, int k)
-{
-	uint64_t r = 0, y = x;
-	for (int i = 0; i < k; ++i, y >>= 2) r = (r << 2) | (3u - (y & 3u));
-	return r < x ? r : x;
-}
-
-} // namespace
-
-struct vc_patterns {
-	std::vector<Pattern> a;
-};
-
-extern "C" int vc_patterns_load(const char *path, vc_patterns **out)
-{
-	if (!path || !out) return VC_EINVAL;
-	*out = nullptr;
-	FILE *fp = fopen(path, "r");
-	if (!fp) return VC_EIO;
-	vc_patterns *db = new (std::nothrow) vc_patterns;
-	if (!db) {
-		fclose(fp);
-		return VC_ENOMEM;
-	}
-	// One record buffer reused across records, like the reference's local
-	// pattern_t: a k-mer string shorter than k is followed by its NUL and by
-	// bytes of earlier longer strings (the reference's buffer starts as
-	// uninitialised stack; this one starts zeroed).
-	Pattern rec;
-	memset(&rec, 0, sizeof(rec));
-	while (fscanf(fp, "%255s%d%d%255s %c %c%127s%127s", rec.chr, &rec.start, &rec.end, rec.rsid,
-	              &rec.ref, &rec.alt, rec.ref_kmer, rec.alt_kmer) == 8)
-		db->a.push_back(rec);
-	fclose(fp);
-	*out = db;
-	return VC_OK;
-}
-
-extern "C" void vc_patterns_free(vc_patterns *db) { delete db; }
-
-extern "C" int vc_patterns_count(const vc_patterns *db) { return db ? (int)db->a.size() : 0; }
-
-extern "C" int vc_pattern_fields(const vc_patterns *db, int i, const char **chr, int *start,
-                                 const char **rsid, char *ref, char *alt, const char **ref_kmer,
-                                 const char **alt_kmer)
-{
-	if (!db || i < 0 || (size_t)i >= db->a.size()) return VC_EINVAL;
-	const Pattern &p = db->a[(size_t)i];
-	if (chr) *chr = p.chr;
-	if (start) *start = p.start;
-	if (rsid) *rsid = p.rsid;
-	if (ref) *ref = p.ref;
-	if (alt) *alt = p.alt;
-	if (ref_kmer) *ref_kmer = p.ref_kmer;
-	if (alt_kmer) *alt_kmer = p.alt_kmer;
-	return VC_OK;
-}
-
-extern "C" void vc_free(void *p) { free(p); }
-
-extern "C" int vc_patterns_keys(const vc_patterns *db, int k, uint64_t **keys, uint32_t **vals,
-                                size_t *n_keys, int *n_collisions)
-{
-	if (!db || !keys || !vals || !n_keys || k < 1 || k > 31) return VC_EINVAL;
-	const size_t n = db->a.size();
-	if (n > (size_t)(INT32_MAX >> 1)) return VC_ETOOMANY;   // vaf-counter.c:205-209
-	init_nt4();
-	uint64_t *K = (uint64_t *)malloc((2 * n + 1) * sizeof(uint64_t));
-	uint32_t *V = (uint32_t *)malloc((2 * n + 1) * sizeof(uint32_t));
-	if (!K || !V) {
-		free(K);
-		free(V);
-		return VC_ENOMEM;
-	}
-	std::unordered_map<uint64_t, uint32_t> seen;
-	seen.reserve(2 * n + 1);
-	size_t m = 0;
-	int coll = 0;
-	for (size_t i = 0; i < n; ++i) {
-		for (int allele = 0; allele < 2; ++allele) {
-			const char *s = allele ? db->a[i].alt_kmer : db->a[i].ref_kmer;
-			uint64_t x = string_key(s, k);
-			if (x == UINT64_MAX) continue;
-			uint64_t c = canonical(x, k);
-			uint32_t v = ((uint32_t)i << 1) | (uint32_t)allele;
-			if (seen.emplace(c, v).second) {
-				K[m] = c;
-				V[m] = v;
-				++m;
-			} else {
-				++coll;                     // first insert wins (khashl.h:218)
-			}
-		}
-	}
-	*keys = K;
-	*vals = V;
-	*n_keys = m;
-	if (n_collisions) *n_collisions = coll;
-	return VC_OK;
-}
-
-extern "C" int vc_write_vaf(const vc_patterns *db, const uint32_t *counts, const char *path)
-{
-	if (!db || !path) return VC_EINVAL;
-	const size_t n = db->a.size();
-	uint64_t tot_ref = 0, tot_alt = 0;
-	for (size_t i = 0; i < n; ++i) {
-		tot_ref += counts ? counts[2 * i] : 0;
-		tot_alt += counts ? counts[2 * i + 1] : 0;
-	}
-	const double avg = (double)(tot_ref + tot_alt) / (n > 0 ? (double)n : 1.0);
-	FILE *fp = fopen(path, "w");
-	if (!fp) return VC_EIO;
-	setvbuf(fp, nullptr, _IOFBF, 1 << 20);
-	fprintf(fp, "# Average depth: %.2f\n", avg);
-	fprintf(fp, "CHR\tPOS\tRSID\tREF\tALT\tREF_COUNT\tALT_COUNT\tTOTAL_COUNT\tVAF\n");
-	for (size_t i = 0; i < n; ++i) {
-		const Pattern &p = db->a[i];
-		const uint32_t rc = counts ? counts[2 * i] : 0, ac = counts ? counts[2 * i + 1] : 0;
-		const uint32_t tot = rc + ac;                       // u32 wrap, as the reference
-		const double vaf = tot > 0 ? (double)ac / tot : 0.0;
-		fprintf(fp, "%s\t%d\t%s\t%c\t%c\t%u\t%u\t%u\t%.4f\n", p.chr, p.start, p.rsid, p.ref, p.alt, rc,
-		        ac, tot, vaf);
-	}
-	return fclose(fp) == 0 ? VC_OK : VC_EIO;
-}
+#include "vafc_stage.h"
 
 // ---------------------------------------------------------------------------
 // device context
 // ---------------------------------------------------------------------------
-
-namespace {
-
-struct Slot {
-	uint8_t *h_seq = nullptr;     // pinned
-	uint64_t *h_offs = nullptr;
-	uint32_t *h_lens = nullptr;
-	uint8_t *d_seq = nullptr;
-	uint64_t *d_offs = nullptr;
-	uint32_t *d_lens = nullptr;
-	size_t cap_bytes = 0, cap_reads = 0;
-	hipEvent_t done = nullptr;
-	hipEvent_t copied = nullptr;  // parallel reader: the slot's H2D copies (copy stream) are done
-	bool pending = false;
-	void *map = nullptr;          // one registered mapping holds h_seq, h_offs, h_lens (slot_alloc_mapped)
-	size_t map_len = 0;
-	bool d_one = false;           // d_offs, d_lens point into d_seq's allocation
-};
-
-} // namespace
 
 struct vc_ctx {
 	int dev = 0, k = 21;
@@ -271,17 +73,13 @@ struct vc_ctx {
 	uint8_t *d_pad = nullptr;              // 64 B staging for inputs under 16 B (kernels load 16 B)
 	uint32_t *d_long = nullptr;
 	uint32_t long_cap = 0;
-	Slot slot[2];
-	int cur = 0;
-	std::vector<Slot> islot;               // parallel ingest (vc_count_file on plain files)
+	VcStager stage;                        // host batches (vc_count_block, the sequential file pass)
+	std::vector<VcSlot> islot;             // parallel ingest (vc_count_file on plain files)
 	hipStream_t cst = nullptr;             // the parallel reader's H2D copies (created on first use)
 	bool ingest_warm = false;              // a parallel-reader pass has completed: its slots are pinned
 	bool timing = false, timed = false;
 	hipEvent_t t0 = nullptr, t1 = nullptr;
-	// vc_count_device on a stream other than st: st's work so far -> that
-	// stream (ev_in), and the launch -> st (ev_out), so that vc_reset, vc_finish
-	// and the shard sum, all on st, stay ordered with it (created on first use)
-	hipEvent_t ev_in = nullptr, ev_out = nullptr;
+	VcStreamBridge bridge;            // vc_count_device on a stream other than st
 	VcCpuSet cpus;                    // the GPUs' NUMA-node CPUs for the reader threads (gpu_cpus)
 	int cpus_threads = -1;            // the thread count cpus was computed for
 	struct Kc *kc = nullptr;               // histogram mode (vc_kc_create)
@@ -292,6 +90,8 @@ struct vc_ctx {
 	std::vector<int> comm_shard;           // the shard each rank reduces
 	uint64_t rr = 0;                       // host batches dealt so far (round robin)
 	uint64_t batches = 0;                  // batches counted by this shard (vc_shard_info)
+
+	int submit(size_t bytes, uint64_t n_reads);   // the acquired slot of `stage`: H2D copies + kernels
 };
 
 static inline int n_shards(const vc_ctx *c) { return 1 + (int)c->rep.size(); }
@@ -474,7 +274,7 @@ extern "C" int vc_create(vc_ctx **out, int k, const uint64_t *keys, const uint32
 	TRY(hipMemset(c->d_tally, 0, sizeof(unsigned long long)));
 	TRY(hipEventCreate(&c->t0));
 	TRY(hipEventCreate(&c->t1));
-	for (auto &s : c->slot) TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+	if ((rc = c->stage.init()) != VC_OK) goto fail;
 	if ((rc = ensure_long_cap(c, (uint64_t)1 << 30)) != VC_OK) goto fail;
 #undef TRY
 	*out = c;
@@ -482,34 +282,6 @@ extern "C" int vc_create(vc_ctx **out, int k, const uint64_t *keys, const uint32
 fail:
 	vc_destroy(c);
 	return rc;
-}
-
-static void free_slot(Slot &s)
-{
-	if (s.map) {
-		(void)hipHostUnregister(s.map);
-		munmap(s.map, s.map_len);
-	} else {
-		if (s.h_seq) (void)hipHostFree(s.h_seq);
-		if (s.h_offs) (void)hipHostFree(s.h_offs);
-		if (s.h_lens) (void)hipHostFree(s.h_lens);
-	}
-	if (s.d_seq) (void)hipFree(s.d_seq);
-	if (!s.d_one) {
-		if (s.d_offs) (void)hipFree(s.d_offs);
-		if (s.d_lens) (void)hipFree(s.d_lens);
-	}
-	s.map = nullptr;
-	s.map_len = 0;
-	s.d_one = false;
-	s.h_seq = nullptr;
-	s.h_offs = nullptr;
-	s.h_lens = nullptr;
-	s.d_seq = nullptr;
-	s.d_offs = nullptr;
-	s.d_lens = nullptr;
-	s.cap_bytes = s.cap_reads = 0;
-	s.pending = false;
 }
 
 static void rccl_comms_destroy(vc_ctx *c);
@@ -522,20 +294,12 @@ extern "C" void vc_destroy(vc_ctx *c)
 	c->rep.clear();
 	(void)hipSetDevice(c->dev);
 	if (c->st) (void)hipStreamSynchronize(c->st);
-	for (auto &s : c->slot) {
-		free_slot(s);
-		if (s.done) (void)hipEventDestroy(s.done);
-	}
-	for (auto &s : c->islot) {
-		free_slot(s);
-		if (s.done) (void)hipEventDestroy(s.done);
-		if (s.copied) (void)hipEventDestroy(s.copied);
-	}
+	c->stage.destroy();
+	for (VcSlot &s : c->islot) vc_slot_destroy(s);
 	if (c->cst) (void)hipStreamDestroy(c->cst);
 	if (c->t0) (void)hipEventDestroy(c->t0);
 	if (c->t1) (void)hipEventDestroy(c->t1);
-	if (c->ev_in) (void)hipEventDestroy(c->ev_in);
-	if (c->ev_out) (void)hipEventDestroy(c->ev_out);
+	c->bridge.destroy();
 	if (c->d_table) (void)hipFree(c->d_table);
 	if (c->d_filter) (void)hipFree(c->d_filter);
 	if (c->d_l2f) (void)hipFree(c->d_l2f);
@@ -709,64 +473,19 @@ extern "C" int vc_count_device(vc_ctx *c, const uint8_t *d_seq, size_t seq_bytes
 	// is torch's default stream), as for every HIP API; VC_STREAM_CTX is the
 	// counter's own non-blocking stream
 	const hipStream_t st = stream == VC_STREAM_CTX ? c->st : (hipStream_t)stream;
-	if (st == c->st) return launch(c, d_seq, seq_bytes, d_offs, d_lens, n_reads, st);
-	if (!c->ev_in) HIPCK(hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
-	if (!c->ev_out) HIPCK(hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming));
-	HIPCK(hipEventRecord(c->ev_in, c->st));           // e.g. a vc_reset before this call
-	HIPCK(hipStreamWaitEvent(st, c->ev_in, 0));
-	const int rc = launch(c, d_seq, seq_bytes, d_offs, d_lens, n_reads, st);
-	if (rc != VC_OK) return rc;
-	HIPCK(hipEventRecord(c->ev_out, st));
-	HIPCK(hipStreamWaitEvent(c->st, c->ev_out, 0));   // vc_finish waits on c->st only
-	return VC_OK;
+	int rc = c->bridge.enter(c->st, st);
+	if (rc == VC_OK) rc = launch(c, d_seq, seq_bytes, d_offs, d_lens, n_reads, st);
+	if (rc == VC_OK) rc = c->bridge.leave(c->st, st);
+	return rc;
 }
 
-static int slot_reserve(Slot &s, size_t bytes, size_t reads)
+int vc_ctx::submit(size_t bytes, uint64_t n_reads)
 {
-	if (bytes <= s.cap_bytes && reads <= s.cap_reads) return VC_OK;
-	if (s.pending) HIPCK(hipEventSynchronize(s.done));
-	s.pending = false;
-	size_t nb = s.cap_bytes > bytes ? s.cap_bytes : bytes + bytes / 4 + 4096;
-	size_t nr = s.cap_reads > reads ? s.cap_reads : reads + reads / 4 + 1024;
-	free_slot(s);
-	HIPCK(hipHostMalloc(&s.h_seq, nb, hipHostMallocDefault));
-	HIPCK(hipHostMalloc(&s.h_offs, nr * sizeof(uint64_t), hipHostMallocDefault));
-	HIPCK(hipHostMalloc(&s.h_lens, nr * sizeof(uint32_t), hipHostMallocDefault));
-	HIPCK(hipMalloc(&s.d_seq, nb));
-	HIPCK(hipMalloc(&s.d_offs, nr * sizeof(uint64_t)));
-	HIPCK(hipMalloc(&s.d_lens, nr * sizeof(uint32_t)));
-	s.cap_bytes = nb;
-	s.cap_reads = nr;
-	return VC_OK;
-}
-
-// Wait until a slot's previous batch has left its pinned buffers.
-static int slot_acquire(vc_ctx *c, Slot **out)
-{
-	Slot &s = c->slot[c->cur];
-	if (s.pending) {
-		HIPCK(hipEventSynchronize(s.done));
-		s.pending = false;
-	}
-	*out = &s;
-	return VC_OK;
-}
-
-// H2D copy of a filled slot + kernels; the slot is released by its event.
-static int slot_submit(vc_ctx *c, Slot &s, size_t bytes, uint64_t n_reads)
-{
-	if (n_reads) {
-		HIPCK(hipMemcpyAsync(s.d_seq, s.h_seq, bytes, hipMemcpyHostToDevice, c->st));
-		HIPCK(hipMemcpyAsync(s.d_offs, s.h_offs, n_reads * sizeof(uint64_t), hipMemcpyHostToDevice, c->st));
-		HIPCK(hipMemcpyAsync(s.d_lens, s.h_lens, n_reads * sizeof(uint32_t), hipMemcpyHostToDevice, c->st));
-		int rc = launch(c, s.d_seq, bytes, s.d_offs, s.d_lens, n_reads, c->st, any_long(s.h_lens, n_reads));
-		if (rc != VC_OK) return rc;
-		HIPCK(hipEventRecord(s.done, c->st));
-		s.pending = true;
-		++c->batches;
-	}
-	c->cur ^= 1;
-	return VC_OK;
+	return stage.submit(bytes, n_reads, st, [&](const VcSlot &s) {
+		const int rc = launch(this, s.d_seq, bytes, s.d_offs, s.d_lens, n_reads, st, any_long(s.h_lens, n_reads));
+		batches += rc == VC_OK ? 1 : 0;
+		return rc;
+	});
 }
 
 extern "C" int vc_count_block(vc_ctx *c, const uint8_t *seq, size_t seq_bytes, const uint64_t *offs,
@@ -778,14 +497,14 @@ extern "C" int vc_count_block(vc_ctx *c, const uint8_t *seq, size_t seq_bytes, c
 		if (offs[i] + lens[i] > seq_bytes) return VC_EINVAL;
 	c = next_shard(c);
 	HIPCK(hipSetDevice(c->dev));
-	Slot *s;
-	int rc = slot_acquire(c, &s);
-	if (rc == VC_OK) rc = slot_reserve(*s, seq_bytes, n_reads);
+	VcSlot *s;
+	int rc = c->stage.acquire(&s);
+	if (rc == VC_OK) rc = vc_slot_reserve(*s, seq_bytes, n_reads);
 	if (rc != VC_OK) return rc;
 	memcpy(s->h_seq, seq, seq_bytes);
 	memcpy(s->h_offs, offs, n_reads * sizeof(uint64_t));
 	memcpy(s->h_lens, lens, n_reads * sizeof(uint32_t));
-	return slot_submit(c, *s, seq_bytes, n_reads);
+	return c->submit(seq_bytes, n_reads);
 }
 
 static int reduce_shards(vc_ctx *c);
@@ -815,7 +534,7 @@ extern "C" int vc_finish(vc_ctx *c, uint32_t *counts, uint64_t *kmers)
 	}
 	HIPCK(hipSetDevice(c->dev));
 	HIPCK(hipStreamSynchronize(c->st));
-	for (auto &s : c->slot) s.pending = false;
+	c->stage.settle();
 	if (c->kc) {   // histogram mode: the k-mers seen (vc_kc_histogram gives the rest)
 		if (kmers) {
 			unsigned long long st[3];
@@ -1108,72 +827,6 @@ extern "C" int vc_shard_info(const vc_ctx *c, int i, int *device, uint64_t *batc
 #define VC_BATCH_BYTES ((size_t)64 << 20)
 #endif
 
-namespace {
-
-// Accepted reads are written straight into a pinned slot; a full slot is
-// shipped to the device and the other slot is filled meanwhile.  With several
-// shards each batch goes to the next shard (its own slots, stream and device).
-struct BatchWriter {
-	vc_ctx *c;
-	vc_ctx *sh = nullptr;         // shard of the open slot
-	Slot *s = nullptr;
-	size_t bytes = 0, limit = VC_BATCH_BYTES;
-	uint64_t n = 0;
-	int err = VC_OK;
-
-	explicit BatchWriter(vc_ctx *ctx) : c(ctx)
-	{
-		const char *e = getenv("VAFC_BATCH_BYTES");   // test knob: smaller batches
-		if (e && atoll(e) >= 1) limit = (size_t)atoll(e);
-	}
-
-	int open_slot()
-	{
-		sh = next_shard(c);
-		if (hipSetDevice(sh->dev) != hipSuccess) return VC_EHIP;
-		int rc = slot_acquire(sh, &s);
-		if (rc == VC_OK) rc = slot_reserve(*s, VC_BATCH_BYTES, VC_BATCH_BYTES / 64);
-		bytes = 0;
-		n = 0;
-		return rc;
-	}
-	int flush()
-	{
-		if (!s) return VC_OK;
-		int rc = slot_submit(sh, *s, bytes, n);
-		s = nullptr;
-		bytes = 0;
-		n = 0;
-		return rc;
-	}
-	int add(const char *seq, size_t len)
-	{
-		if (!s && (err = open_slot()) != VC_OK) return err;
-		if (bytes + len > s->cap_bytes || n + 1 > s->cap_reads || (n > 0 && bytes + len > limit)) {
-			if (n > 0) {
-				if ((err = flush()) != VC_OK) return err;
-				if ((err = open_slot()) != VC_OK) return err;
-			}
-			if (len > s->cap_bytes && (err = slot_reserve(*s, len, 1)) != VC_OK) return err;
-		}
-		memcpy(s->h_seq + bytes, seq, len);
-		s->h_offs[n] = bytes;
-		s->h_lens[n] = (uint32_t)len;
-		bytes += len;
-		++n;
-		return VC_OK;
-	}
-};
-
-double wall_now()
-{
-	struct timespec ts;
-	clock_gettime(CLOCK_MONOTONIC, &ts);
-	return ts.tv_sec + ts.tv_nsec * 1e-9;
-}
-
-} // namespace
-
 // ---------------------------------------------------------------------------
 // parallel ingest of plain files (vafc_ingest.h): pieces parsed by -t worker
 // threads straight into pinned slots, shipped to the device in file order
@@ -1186,7 +839,7 @@ double wall_now()
 #define VC_PIECE_BYTES_WARM ((uint64_t)32 << 20)
 #endif
 
-static int ingest_slot_alloc(Slot &s, uint64_t piece);
+static int ingest_slot_alloc(VcSlot &s, uint64_t piece);
 static size_t ingest_slot_bytes(uint64_t piece);
 
 namespace {
@@ -1199,46 +852,24 @@ public:
 	int acquire(int slot, VcSlotBuf *b) override
 	{
 		vc_ctx *sh;
-		Slot &s = at(slot, &sh);
+		VcSlot &s = at(slot, &sh);
 		HIPCK(hipSetDevice(sh->dev));
-		if (s.pending) {
-			HIPCK(hipEventSynchronize(s.done));
-			s.pending = false;
-		}
+		int rc = vc_slot_wait(s);
+		if (rc != VC_OK) return rc;
 		// first use of the slot (reserve_ingest_slots, alloc = false), or
 		// buffers sized for smaller pieces than this pass's
-		if (!s.h_seq || s.cap_bytes < ingest_slot_bytes(piece_)) {
-			const int rc = ingest_slot_alloc(s, piece_);
-			if (rc != VC_OK) return rc;
-		}
-		fill(s, b);
-		return VC_OK;
+		if (!s.h_seq || s.cap_bytes < ingest_slot_bytes(piece_)) rc = ingest_slot_alloc(s, piece_);
+		if (rc == VC_OK) fill(s, b);
+		return rc;
 	}
 	int grow(int slot, VcSlotBuf *b, size_t bytes, size_t reads, size_t used_bytes, size_t used_reads) override
 	{
 		vc_ctx *sh;
-		Slot &s = at(slot, &sh);
+		VcSlot &s = at(slot, &sh);
 		HIPCK(hipSetDevice(sh->dev));
-		Slot n;
-		n.done = s.done;
-		n.copied = s.copied;
-		if (hipHostMalloc(&n.h_seq, bytes, hipHostMallocDefault) != hipSuccess ||
-		    hipHostMalloc(&n.h_offs, reads * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess ||
-		    hipHostMalloc(&n.h_lens, reads * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess ||
-		    hipMalloc(&n.d_seq, bytes) != hipSuccess || hipMalloc(&n.d_offs, reads * sizeof(uint64_t)) != hipSuccess ||
-		    hipMalloc(&n.d_lens, reads * sizeof(uint32_t)) != hipSuccess) {
-			free_slot(n);
-			return VC_EHIP;
-		}
-		n.cap_bytes = bytes;
-		n.cap_reads = reads;
-		memcpy(n.h_seq, s.h_seq, used_bytes);
-		memcpy(n.h_offs, s.h_offs, used_reads * sizeof(uint64_t));
-		memcpy(n.h_lens, s.h_lens, used_reads * sizeof(uint32_t));
-		free_slot(s);
-		s = n;
-		fill(s, b);
-		return VC_OK;
+		const int rc = vc_slot_realloc(s, bytes, reads, used_bytes, used_reads);   // exact sizes: the reader's growth rule
+		if (rc == VC_OK) fill(s, b);
+		return rc;
 	}
 	// The copies go on the shard's copy stream and the kernels on its own
 	// stream, ordered by one event per slot: the DMA engine streams the pieces
@@ -1248,7 +879,7 @@ public:
 	int submit(int slot, const VcSlotBuf &, uint64_t n, uint64_t bytes) override
 	{
 		vc_ctx *sh;
-		Slot &s = at(slot, &sh);
+		VcSlot &s = at(slot, &sh);
 		HIPCK(hipSetDevice(sh->dev));
 		if (!sh->cst) HIPCK(hipStreamCreateWithFlags(&sh->cst, hipStreamNonBlocking));
 		if (!s.copied) HIPCK(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
@@ -1269,12 +900,12 @@ private:
 	vc_ctx *c_;
 	int n_;
 	uint64_t piece_;
-	Slot &at(int slot, vc_ctx **sh)
+	VcSlot &at(int slot, vc_ctx **sh)
 	{
 		*sh = shard_at(c_, slot % n_);
 		return (*sh)->islot[(size_t)(slot / n_)];
 	}
-	static void fill(const Slot &s, VcSlotBuf *b)
+	static void fill(const VcSlot &s, VcSlotBuf *b)
 	{
 		b->seq = s.h_seq;
 		b->offs = s.h_offs;
@@ -1328,7 +959,7 @@ static size_t ingest_slot_bytes(uint64_t piece) { return (size_t)piece / 2 + ((s
 // 52 GB/s H2D (tools/pin_probe.hip, profiles/r06b_pin_probe.log).  The CLI pins
 // its slots inside the counting timer, as the reference allocates its block
 // buffers inside it.  VAFC_PIN=malloc keeps hipHostMalloc (A/B).
-static int slot_alloc_mapped(Slot &s, size_t bytes, size_t reads)
+static int slot_alloc_mapped(VcSlot &s, size_t bytes, size_t reads)
 {
 	const size_t huge = (size_t)2 << 20;
 	const size_t ob = (bytes + 63) / 64 * 64, lb = ob + reads * sizeof(uint64_t);
@@ -1369,15 +1000,15 @@ static int slot_alloc_mapped(Slot &s, size_t bytes, size_t reads)
 	return VC_OK;
 }
 
-static int ingest_slot_alloc(Slot &s, uint64_t piece)
+static int ingest_slot_alloc(VcSlot &s, uint64_t piece)
 {
 	static const bool use_malloc = getenv("VAFC_PIN") && !strcmp(getenv("VAFC_PIN"), "malloc");
-	if (use_malloc) return slot_reserve(s, ingest_slot_bytes(piece), (size_t)piece / 256 + 4096);
 	const size_t bytes = ingest_slot_bytes(piece), reads = (size_t)piece / 256 + 4096;
+	if (use_malloc) return vc_slot_reserve(s, bytes, reads);
 	if (bytes <= s.cap_bytes && reads <= s.cap_reads) return VC_OK;
-	if (s.pending) HIPCK(hipEventSynchronize(s.done));
-	s.pending = false;
-	free_slot(s);
+	const int rc = vc_slot_wait(s);
+	if (rc != VC_OK) return rc;
+	vc_slot_free(s);
 	return slot_alloc_mapped(s, bytes + bytes / 4 + 4096, reads + reads / 4 + 1024);
 }
 
@@ -1394,7 +1025,7 @@ static int reserve_ingest_slots(vc_ctx *c, size_t slots, bool alloc)
 			HIPCK(hipEventCreateWithFlags(&c->islot[i].done, hipEventDisableTiming));
 	}
 	for (size_t i = 0; alloc && i < slots; ++i) {
-		Slot &s = c->islot[i];
+		VcSlot &s = c->islot[i];
 		if (s.h_seq) continue;
 		int rc = ingest_slot_alloc(s, VC_PIECE_BYTES);
 		if (rc != VC_OK) return rc;
@@ -1421,9 +1052,7 @@ static int count_file_parallel(vc_ctx *c, int fd, uint64_t size, int block_bases
 	// copies, kernels and events per byte (profiles/r05i_*: 39.7-40.5 against
 	// 35.5-36.1 Gbases/s in one process; in a fresh CLI process the 32 MB
 	// slots' pinning made the pass 40 % slower, profiles/r05i_cli_piece_ab.json)
-	const char *pe = getenv("VAFC_INGEST_PIECE");          // test knob: piece size in bytes
-	const uint64_t piece = pe && atoll(pe) >= 2 ? (uint64_t)atoll(pe)
-	                                            : (c->ingest_warm ? VC_PIECE_BYTES_WARM : VC_PIECE_BYTES);
+	const uint64_t piece = vc_ingest_piece(c->ingest_warm ? VC_PIECE_BYTES_WARM : VC_PIECE_BYTES);
 	DeviceSink sink(c, piece);
 	const int rc = vc_ingest_plain(fd, size, c->k, block_bases, threads, slots, piece, sink, st, range);
 	if (rc == VC_OK) c->ingest_warm = true;
@@ -1437,8 +1066,7 @@ static int count_file_gzip(vc_ctx *c, VcGzParallel *g, int block_bases, int n_th
 	const int parsers = vc_gz_parse_threads(clamp_threads(n_threads));
 	const int slots = reserve_ingest(c, parsers, false);
 	if (slots < 0) return slots;
-	const char *pe = getenv("VAFC_INGEST_PIECE");          // test knob: piece size in bytes
-	const uint64_t piece = pe && atoll(pe) >= 2 ? (uint64_t)atoll(pe) : VC_PIECE_BYTES;
+	const uint64_t piece = vc_ingest_piece(VC_PIECE_BYTES);
 	DeviceSink sink(c, piece);
 	return vc_ingest_gzip(g, c->k, block_bases, parsers, slots, piece, (uint64_t)(slots + 2) * piece * 2, sink, st);
 }
@@ -1512,107 +1140,130 @@ static VcCpuSet gpu_cpus(vc_ctx *c, int threads)
 	return out;
 }
 
+// The CPUs for the reader threads of a pass with `threads` (clamped) of them,
+// on the GPU's NUMA node when it has a CPU for each: the parse workers, or
+// for gzip the inflaters, the parsers of the inflated text, the pump and the
+// block loop.
+static VcCpuSet reader_cpus(vc_ctx *c, int threads, bool gz)
+{
+	return gpu_cpus(c, gz ? vc_gz_inflate_threads(threads) + vc_gz_parse_threads(threads) + 2 : threads);
+}
+
+namespace {
+
+// What every file pass keeps: its stats, zeroed, and its start.
+struct FilePass {
+	vc_ctx *c;                 // NULL: nothing was queued on a device (vc_scan_file)
+	vc_file_stats *out;
+	vc_file_stats st = {0, 0, 0, 0.0};
+	double t0 = vc_now();
+
+	FilePass(vc_ctx *ctx, vc_file_stats *o) : c(ctx), out(o) {}
+	// Every exit of a pass: wait for the shards' queued batches, stop the clock
+	// and hand the stats out.
+	int finish(int rc)
+	{
+		if (rc == VC_OK && c) rc = sync_shards(c);
+		st.seconds = vc_now() - t0;
+		if (out) *out = st;
+		return rc;
+	}
+};
+
+struct FileKind {
+	int fd = -1;               // open iff the path is a regular file: the caller closes it
+	bool regular = false, gzip = false;
+	uint64_t size = 0;
+};
+
+// A path that is not a regular file (a FIFO, a device) is never opened here:
+// it is opened exactly once, by the sequential reader; opening it only to look
+// at it would let a pipe's writer see its reader go away (a pipe is read once,
+// as the reference does).  False: the path cannot be read.
+bool classify(const char *path, FileKind *f)
+{
+	struct stat sb;
+	if (stat(path, &sb) != 0) return false;
+	if (!S_ISREG(sb.st_mode)) return true;
+	if ((f->fd = open(path, O_RDONLY)) < 0) return false;
+	uint8_t magic[2] = {0, 0};
+	f->regular = fstat(f->fd, &sb) == 0 && S_ISREG(sb.st_mode);
+	f->gzip = f->regular && pread(f->fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+	f->size = f->regular ? (uint64_t)sb.st_size : 0;
+	return true;
+}
+
+} // namespace
+
 extern "C" int vc_count_file(vc_ctx *c, const char *path, int block_bases, int n_threads,
                              vc_file_stats *st)
 {
 	if (!c || !path) return VC_EINVAL;
-	vc_file_stats local = {0, 0, 0, 0.0};
-	const double t0 = wall_now();
 	HIPCK(hipSetDevice(c->dev));
-	// a path that is not a regular file (a FIFO, a device) is opened exactly
-	// once, by the sequential reader below: opening it here only to look at
-	// it would let a pipe's writer see its reader go away
-	struct stat sb;
-	if (stat(path, &sb) != 0) return VC_EIO;
-	const int fd = S_ISREG(sb.st_mode) ? open(path, O_RDONLY) : -1;
-	if (S_ISREG(sb.st_mode) && fd < 0) return VC_EIO;
-	uint8_t magic[2] = {0, 0};
-	const bool reg = fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode);
-	const bool gz = reg && pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
-	const bool plain = reg && !gz;
-	// the reader threads spawned below run on the GPU's NUMA node when it has
-	// a CPU for each of them: the parse workers, or for gzip the inflaters,
-	// the parsers of the inflated text, the pump and the block loop
+	FilePass fp(c, st);
+	FileKind f;
+	if (!classify(path, &f)) return fp.finish(VC_EIO);
 	const int t = clamp_threads(n_threads);
-	VcAffinityScope placement(gpu_cpus(c, gz ? vc_gz_inflate_threads(t) + vc_gz_parse_threads(t) + 2 : t));
-	{
-		const char *me = getenv("VAFC_INGEST_MIN");        // test knob: smallest file for the parallel reader
-		const uint64_t min_bytes = me ? (uint64_t)atoll(me) : VC_PARALLEL_MIN_BYTES;
-		if (plain && (uint64_t)sb.st_size >= min_bytes && sb.st_size > 0) {
-			int rc = count_file_parallel(c, fd, (uint64_t)sb.st_size, block_bases, n_threads, local);
-			close(fd);
-			if (rc == VC_OK) rc = sync_shards(c);
-			local.seconds = wall_now() - t0;
-			if (st) *st = local;
-			return rc;
-		}
-		if (fd >= 0) close(fd);
-		if (gz) {   // parallel inflate + parallel parse (falls through if the inflater declines the file)
-			const char *ce = getenv("VAFC_GZ_CHUNK");            // test knob: compressed bytes per chunk
-			VcGzParallel *g = vc_gzp_open(path, vc_gz_inflate_threads(clamp_threads(n_threads)),
-			                              ce ? (uint64_t)atoll(ce) : 0);
-			if (g) {
-				int rc = count_file_gzip(c, g, block_bases, n_threads, local);
-				vc_gzp_close(g);
-				if (rc == VC_OK) rc = sync_shards(c);
-				local.seconds = wall_now() - t0;
-				if (st) *st = local;
-				return rc;
-			}
+	VcAffinityScope placement(reader_cpus(c, t, f.gzip));
+	const char *me = getenv("VAFC_INGEST_MIN");        // test knob: smallest file for the parallel reader
+	const uint64_t min_bytes = me ? (uint64_t)atoll(me) : VC_PARALLEL_MIN_BYTES;
+	if (f.regular && !f.gzip && f.size >= min_bytes && f.size > 0) {
+		const int rc = count_file_parallel(c, f.fd, f.size, block_bases, n_threads, fp.st);
+		close(f.fd);
+		return fp.finish(rc);
+	}
+	if (f.fd >= 0) close(f.fd);
+	if (f.gzip) {   // parallel inflate + parallel parse (falls through if the inflater declines the file)
+		VcGzParallel *g = vc_gzp_open(path, vc_gz_inflate_threads(t), vc_gz_chunk());
+		if (g) {
+			const int rc = count_file_gzip(c, g, block_bases, n_threads, fp.st);
+			vc_gzp_close(g);
+			return fp.finish(rc);
 		}
 	}
 	VcFastqReader rd;   // small plain files, pipes, gzip the inflater declines
-	if (!rd.open_parallel(path, clamp_threads(n_threads))) return VC_EIO;
-	BatchWriter bw(c);
-	int rc = vc_block_loop(rd, c->k, block_bases,
-	                    [&bw](const char *s, size_t l) { return bw.add(s, l); }, local);
+	if (!rd.open_parallel(path, t)) return fp.finish(VC_EIO);
+	// with several shards each batch goes to the next shard (its own slots,
+	// stream and device)
+	const size_t limit = vc_batch_bytes(VC_BATCH_BYTES);
+	VcBatchWriter bw(limit, limit / 64, [c]() -> vc_ctx * {
+		vc_ctx *sh = next_shard(c);
+		return hipSetDevice(sh->dev) == hipSuccess ? sh : nullptr;
+	});
+	int rc = vc_block_loop(rd, c->k, block_bases, [&bw](const char *s, size_t l) { return bw.add(s, l); }, fp.st);
 	if (rc == VC_OK) rc = bw.flush();
-	if (rc == VC_OK) rc = sync_shards(c);
-	local.seconds = wall_now() - t0;
-	if (st) *st = local;
-	return rc;
+	return fp.finish(rc);
 }
 
 extern "C" int vc_count_file_range(vc_ctx *c, const char *path, uint64_t begin, uint64_t end, int block_bases,
                                    int n_threads, vc_file_stats *st, vc_range_info *ri)
 {
 	if (!c || !path || !ri || end <= begin) return VC_EINVAL;
-	vc_file_stats local = {0, 0, 0, 0.0};
 	*ri = vc_range_info{UINT64_MAX, UINT64_MAX, 0, 0, 1};
-	const double t0 = wall_now();
-	struct stat sb;
-	if (stat(path, &sb) != 0) return VC_EIO;
-	// not a regular file (a FIFO): never opened here, so vc_count_file's
-	// reader is its only reader (a pipe is read once, as the reference does)
-	const int fd = S_ISREG(sb.st_mode) ? open(path, O_RDONLY) : -1;
-	if (S_ISREG(sb.st_mode) && fd < 0) return VC_EIO;
-	uint8_t magic[2] = {0, 0};
-	const bool reg = fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode);
-	const bool gz = reg && pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
-	if (!reg || gz) {   // not split: the first range counts the whole file
-		if (fd >= 0) close(fd);
-		if (begin > 0) {
-			if (st) *st = local;
-			return VC_OK;
+	HIPCK(hipSetDevice(c->dev));
+	FilePass fp(c, st);
+	FileKind f;
+	if (!classify(path, &f)) return fp.finish(VC_EIO);
+	if (!f.regular || f.gzip) {   // not split: the first range counts the whole file
+		if (f.fd >= 0) close(f.fd);
+		int rc = VC_OK;
+		if (begin == 0) {
+			rc = vc_count_file(c, path, block_bases, n_threads, &fp.st);
+			if (rc == VC_OK) *ri = vc_range_info{0, UINT64_MAX, 0, 1, 1};
 		}
-		const int rc = vc_count_file(c, path, block_bases, n_threads, st);
-		if (rc == VC_OK) *ri = vc_range_info{0, UINT64_MAX, 0, 1, 1};
-		return rc;
+		return fp.finish(rc);
 	}
-	int rc = hipSetDevice(c->dev) == hipSuccess ? VC_OK : VC_EHIP;
 	VcTextRange R;
 	R.begin = begin;
 	R.end = end;
-	if (rc == VC_OK) {
-		VcAffinityScope placement(gpu_cpus(c, clamp_threads(n_threads)));
-		rc = count_file_parallel(c, fd, (uint64_t)sb.st_size, block_bases, n_threads, local, &R);
+	int rc;
+	{
+		VcAffinityScope placement(reader_cpus(c, clamp_threads(n_threads), false));
+		rc = count_file_parallel(c, f.fd, f.size, block_bases, n_threads, fp.st, &R);
 	}
-	close(fd);
-	if (rc == VC_OK) rc = sync_shards(c);
+	close(f.fd);
 	*ri = vc_range_info{R.first, R.next, R.errs, R.stopped ? 1u : 0u, 0u};
-	local.seconds = wall_now() - t0;
-	if (st) *st = local;
-	return rc;
+	return fp.finish(rc);
 }
 
 // One share of a gzip file (include/vafc.h, vafc_gzip.h): the inflater (from
@@ -1628,8 +1279,7 @@ static int count_gz_share_g(vc_ctx *c, VcGzParallel *g, int fmt, int parsers, in
 	const size_t np = first_share ? 0 : 1;
 	if (rc >= 0) {
 		const int slots = rc;
-		const char *pe = getenv("VAFC_INGEST_PIECE");          // test knob: piece size in bytes
-		const uint64_t piece = pe && atoll(pe) >= 2 ? (uint64_t)atoll(pe) : VC_PIECE_BYTES;
+		const uint64_t piece = vc_ingest_piece(VC_PIECE_BYTES);
 		DeviceSink sink(c, piece);
 		R.begin = np;
 		R.end = np + text_len;
@@ -1640,7 +1290,6 @@ static int count_gz_share_g(vc_ctx *c, VcGzParallel *g, int fmt, int parsers, in
 	VcGzShareCrc sc;
 	vc_gzp_share_crc(g, &sc);
 	vc_gzp_close(g);
-	if (rc == VC_OK) rc = sync_shards(c);
 	*ri = vc_range_info{R.first == UINT64_MAX ? UINT64_MAX : R.first - np,
 	                    R.next == UINT64_MAX ? UINT64_MAX : R.next - np - text_len, R.errs, R.stopped ? 1u : 0u, 0u};
 	*crc = vc_gz_share_crc{sc.events, sc.head_crc, sc.head_len, sc.head_expect_crc, sc.head_expect_isize,
@@ -1653,24 +1302,19 @@ extern "C" int vc_count_gz_share(vc_ctx *c, const char *path, int first_share, u
                                  vc_file_stats *st, vc_range_info *ri, vc_gz_share_crc *crc)
 {
 	if (!c || !path || !ri || !crc || text_len == 0 || (!first_share && !window)) return VC_EINVAL;
-	vc_file_stats local = {0, 0, 0, 0.0};
 	*ri = vc_range_info{UINT64_MAX, UINT64_MAX, 0, 0, 0};
 	memset(crc, 0, sizeof *crc);
-	const double t0 = wall_now();
 	HIPCK(hipSetDevice(c->dev));
+	FilePass fp(c, st);
 	const int fmt = vc_gz_text_format(path);
-	if (fmt < 0) return VC_EINVAL;
+	if (fmt < 0) return fp.finish(VC_EINVAL);
 	const int t = clamp_threads(n_threads);
-	VcAffinityScope placement(gpu_cpus(c, vc_gz_inflate_threads(t) + vc_gz_parse_threads(t) + 2));
-	const char *ce = getenv("VAFC_GZ_CHUNK");   // test knob: compressed bytes per chunk
-	VcGzParallel *g = vc_gzp_open_share(path, vc_gz_inflate_threads(t), ce ? (uint64_t)atoll(ce) : 0,
-	                                    first_share != 0, start_bit, window, text_len);
-	if (!g) return VC_EIO;
-	const int rc = count_gz_share_g(c, g, fmt, vc_gz_parse_threads(t), first_share, window, text_len, block_bases,
-	                                local, ri, crc);
-	local.seconds = wall_now() - t0;
-	if (st) *st = local;
-	return rc;
+	VcAffinityScope placement(reader_cpus(c, t, true));
+	VcGzParallel *g = vc_gzp_open_share(path, vc_gz_inflate_threads(t), vc_gz_chunk(), first_share != 0, start_bit,
+	                                    window, text_len);
+	if (!g) return fp.finish(VC_EIO);
+	return fp.finish(count_gz_share_g(c, g, fmt, vc_gz_parse_threads(t), first_share, window, text_len, block_bases,
+	                                  fp.st, ri, crc));
 }
 
 extern "C" int vc_gz_share_open(vc_ctx *c, const char *path, uint64_t begin, uint64_t end, int n_threads,
@@ -1686,8 +1330,7 @@ extern "C" int vc_gz_share_open(vc_ctx *c, const char *path, uint64_t begin, uin
 	VcCpuSet none;
 	CPU_ZERO(&none.set);
 	if (c) HIPCK(hipSetDevice(c->dev));
-	const int ct = clamp_threads(t);
-	VcAffinityScope placement(c ? gpu_cpus(c, vc_gz_inflate_threads(ct) + vc_gz_parse_threads(ct) + 2) : none);
+	VcAffinityScope placement(c ? reader_cpus(c, clamp_threads(t), true) : none);
 	VcGzShare sh;
 	VcGzParallel *g = nullptr;
 	if (!vc_gzp_scan_share_hold(path, t, chunk_bytes, begin, end, hold_bytes, &sh, window_sym, &g)) return VC_EIO;
@@ -1711,46 +1354,38 @@ extern "C" int vc_count_gz_share_held(vc_ctx *c, vc_gz_share *h, int first_share
                                       vc_range_info *ri, vc_gz_share_crc *crc)
 {
 	if (!c || !h || !h->g || !ri || !crc || text_len == 0 || (!first_share && !window)) return VC_EINVAL;
-	vc_file_stats local = {0, 0, 0, 0.0};
 	*ri = vc_range_info{UINT64_MAX, UINT64_MAX, 0, 0, 0};
 	memset(crc, 0, sizeof *crc);
-	const double t0 = wall_now();
 	HIPCK(hipSetDevice(c->dev));
-	if (h->format < 0) return VC_EINVAL;
+	FilePass fp(c, st);
+	if (h->format < 0) return fp.finish(VC_EINVAL);
 	const int t = clamp_threads(n_threads);
-	VcAffinityScope placement(gpu_cpus(c, vc_gz_inflate_threads(t) + vc_gz_parse_threads(t) + 2));
+	VcAffinityScope placement(reader_cpus(c, t, true));
 	VcGzParallel *g = h->g;
 	h->g = nullptr;   // counted once; count_gz_share_g closes it
 	if (!vc_gzp_resume_share(g, first_share ? nullptr : window, text_len)) {
 		vc_gzp_close(g);
-		return VC_EINVAL;
+		return fp.finish(VC_EINVAL);
 	}
-	const int rc = count_gz_share_g(c, g, h->format, vc_gz_held_parse_threads(t), first_share, window, text_len,
-	                                block_bases, local, ri, crc);
-	local.seconds = wall_now() - t0;
-	if (st) *st = local;
-	return rc;
+	return fp.finish(count_gz_share_g(c, g, h->format, vc_gz_held_parse_threads(t), first_share, window, text_len,
+	                                  block_bases, fp.st, ri, crc));
 }
 
 extern "C" int vc_scan_file(const char *path, int k, int block_bases, vc_file_stats *st,
                             uint8_t *seq_out, size_t seq_cap, uint32_t *lens_out, size_t lens_cap)
 {
 	if (!path || !st) return VC_EINVAL;
-	vc_file_stats local = {0, 0, 0, 0.0};
-	const double t0 = wall_now();
+	FilePass fp(nullptr, st);
 	VcFastqReader rd;
-	if (!rd.open(path)) return VC_EIO;
+	if (!rd.open(path)) return fp.finish(VC_EIO);
 	size_t nb = 0, nr = 0;
-	int rc = vc_block_loop(rd, k, block_bases, [&](const char *s, size_t l) {
+	return fp.finish(vc_block_loop(rd, k, block_bases, [&](const char *s, size_t l) {
 		if (seq_out && nb + l <= seq_cap) memcpy(seq_out + nb, s, l);
 		if (lens_out && nr < lens_cap) lens_out[nr] = (uint32_t)l;
 		nb += l;
 		++nr;
 		return VC_OK;
-	}, local);
-	local.seconds = wall_now() - t0;
-	*st = local;
-	return rc;
+	}, fp.st));
 }
 
 extern "C" int64_t vc_scan_records(const char *path, int32_t *rets, int64_t cap)

@@ -976,8 +976,7 @@ extern "C" int vc_scan_file_parallel(const char *path, int k, int block_bases, i
 		int rc;
 		VcGzParallel *g = vc_gzp_open(path, vc_gz_inflate_threads(n_threads), piece_bytes);
 		if (g) {
-			const char *pe = getenv("VAFC_INGEST_PIECE");
-			const uint64_t piece = pe && atoll(pe) >= 2 ? (uint64_t)atoll(pe) : ((uint64_t)16 << 20);
+			const uint64_t piece = vc_ingest_piece((uint64_t)16 << 20);
 			const int parsers = vc_gz_parse_threads(n_threads);
 			HostSink sink(parsers + 2, piece, seq_out, seq_cap, lens_out, lens_cap);
 			rc = vc_ingest_gzip(g, k, block_bases, parsers, parsers + 2, piece, (uint64_t)(parsers + 4) * piece * 2,
@@ -1059,8 +1058,7 @@ static int scan_gz_share_g(VcGzParallel *g, int fmt, int k, int first_share, con
                            vc_gz_share_crc *crc, uint8_t *seq_out, size_t seq_cap, uint32_t *lens_out,
                            size_t lens_cap)
 {
-	const char *pe = getenv("VAFC_INGEST_PIECE");
-	const uint64_t piece = pe && atoll(pe) >= 2 ? (uint64_t)atoll(pe) : ((uint64_t)16 << 20);
+	const uint64_t piece = vc_ingest_piece((uint64_t)16 << 20);
 	HostSink sink(parsers + 2, piece, seq_out, seq_cap, lens_out, lens_cap);
 	const size_t np = first_share ? 0 : 1;
 	VcTextRange R;
@@ -1091,9 +1089,8 @@ extern "C" int vc_scan_gz_share(const char *path, int k, int first_share, uint64
 	const double t0 = mono_now();
 	const int fmt = vc_gz_text_format(path);
 	if (fmt < 0) return VC_EINVAL;
-	const char *ce = getenv("VAFC_GZ_CHUNK");   // test knob: compressed bytes per chunk
-	VcGzParallel *g = vc_gzp_open_share(path, vc_gz_inflate_threads(n_threads), ce ? (uint64_t)atoll(ce) : 0,
-	                                    first_share != 0, start_bit, window, text_len);
+	VcGzParallel *g = vc_gzp_open_share(path, vc_gz_inflate_threads(n_threads), vc_gz_chunk(), first_share != 0,
+	                                    start_bit, window, text_len);
 	if (!g) return VC_EIO;
 	const int rc = scan_gz_share_g(g, fmt, k, first_share, window, text_len, block_bases,
 	                               vc_gz_parse_threads(n_threads), local, ri, crc, seq_out, seq_cap, lens_out,

@@ -178,6 +178,19 @@ inline int vc_gz_inflate_threads(int threads)
 	if (e && atoi(e) > 0) return atoi(e);
 	return threads < 1 ? 1 : threads;
 }
+// Test knobs.  $VAFC_INGEST_PIECE: the reader's piece size in bytes (>= 2)
+// instead of dflt.  $VAFC_GZ_CHUNK: compressed bytes per inflate chunk; 0 =
+// sized by the inflater from the file size.
+inline uint64_t vc_ingest_piece(uint64_t dflt)
+{
+	const char *e = getenv("VAFC_INGEST_PIECE");
+	return e && atoll(e) >= 2 ? (uint64_t)atoll(e) : dflt;
+}
+inline uint64_t vc_gz_chunk()
+{
+	const char *e = getenv("VAFC_GZ_CHUNK");
+	return e && atoll(e) > 0 ? (uint64_t)atoll(e) : 0;
+}
 int vc_ingest_gzip(VcGzParallel *g, int k, int block_bases, int threads, int slots, uint64_t piece_bytes,
                    uint64_t window_bytes, VcIngestSink &sink, vc_file_stats &st);
 // One share of a gzip stream (vafc_gzip.h, vc_gzp_open_share): the text is

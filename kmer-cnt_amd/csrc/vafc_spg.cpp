@@ -30,6 +30,7 @@
 #include "vafc_fastq.h"
 #include "vafc_gzip.h"
 #include "vafc_internal.h"
+#include "vafc_stage.h"
 
 struct vc_fasta {
 	std::vector<std::string> names;
@@ -316,15 +317,20 @@ extern "C" int vc_fasta_data(const vc_fasta *fa, const uint8_t **seq, size_t *by
 
 extern "C" void vc_fasta_free(vc_fasta *fa) { delete fa; }
 
-#define SPGCK(call)                                                                          \
-	do {                                                                                     \
-		hipError_t e_ = (call);                                                              \
-		if (e_ != hipSuccess) {                                                              \
-			fprintf(stderr, "[E::vafc] %s failed: %s\n", #call, hipGetErrorString(e_));     \
-			rc = VC_EHIP;                                                                    \
-			goto done;                                                                       \
-		}                                                                                    \
-	} while (0)
+// One synchronous upload of the sequences and their count; the caller frees
+// whatever *d_seq, *d_offs and *d_lens hold afterwards.
+static int count_uploaded(vc_ctx *ctx, const uint8_t *seq, size_t seq_bytes, const uint64_t *offs,
+                          const uint32_t *lens, uint64_t n_seqs, uint8_t **d_seq, uint64_t **d_offs,
+                          uint32_t **d_lens)
+{
+	HIPCK(hipMalloc(d_seq, seq_bytes + 16));
+	HIPCK(hipMemcpy(*d_seq, seq, seq_bytes, hipMemcpyHostToDevice));
+	HIPCK(hipMalloc(d_offs, n_seqs * sizeof(uint64_t)));
+	HIPCK(hipMalloc(d_lens, n_seqs * sizeof(uint32_t)));
+	HIPCK(hipMemcpy(*d_offs, offs, n_seqs * sizeof(uint64_t), hipMemcpyHostToDevice));
+	HIPCK(hipMemcpy(*d_lens, lens, n_seqs * sizeof(uint32_t), hipMemcpyHostToDevice));
+	return vc_count_device(ctx, *d_seq, seq_bytes, *d_offs, *d_lens, n_seqs, nullptr);
+}
 
 extern "C" int vc_count_candidates(int k, const uint8_t *seq, size_t seq_bytes, const uint64_t *offs,
                                    const uint32_t *lens, uint64_t n_seqs, const uint64_t *keys, size_t n_keys,
@@ -345,19 +351,9 @@ extern "C" int vc_count_candidates(int k, const uint8_t *seq, size_t seq_bytes, 
 	uint8_t *d_seq = nullptr;
 	uint64_t *d_offs = nullptr;
 	uint32_t *d_lens = nullptr;
-	if (n_seqs) {
-		SPGCK(hipMalloc(&d_seq, seq_bytes + 16));
-		SPGCK(hipMemcpy(d_seq, seq, seq_bytes, hipMemcpyHostToDevice));
-		SPGCK(hipMalloc(&d_offs, n_seqs * sizeof(uint64_t)));
-		SPGCK(hipMalloc(&d_lens, n_seqs * sizeof(uint32_t)));
-		SPGCK(hipMemcpy(d_offs, offs, n_seqs * sizeof(uint64_t), hipMemcpyHostToDevice));
-		SPGCK(hipMemcpy(d_lens, lens, n_seqs * sizeof(uint32_t), hipMemcpyHostToDevice));
-		rc = vc_count_device(ctx, d_seq, seq_bytes, d_offs, d_lens, n_seqs, nullptr);
-		if (rc != VC_OK) goto done;
-	}
-	rc = vc_finish(ctx, all.data(), nullptr);
+	if (n_seqs) rc = count_uploaded(ctx, seq, seq_bytes, offs, lens, n_seqs, &d_seq, &d_offs, &d_lens);
+	if (rc == VC_OK) rc = vc_finish(ctx, all.data(), nullptr);
 	if (rc == VC_OK) memcpy(counts, all.data(), n_keys * sizeof(uint32_t));
-done:
 	if (d_seq) (void)hipFree(d_seq);
 	if (d_offs) (void)hipFree(d_offs);
 	if (d_lens) (void)hipFree(d_lens);

@@ -783,6 +783,109 @@ def test_count_file_and_pattern_handle(tmp_path):
     assert np.array_equal(got, Statement(qs, reads).counts(11))
 
 
+def batches_of(lens, limit, max_reads):
+    """How many batches the file pass's writer submits (csrc/vafc_stage.h): a
+    batch is closed by the read that would take it past `limit` bytes or
+    `max_reads` reads; a longer read is a batch of its own."""
+    n_batches, nbytes, n = 0, 0, 0
+    for ln in lens:
+        if n and (nbytes + ln > limit or n >= max_reads):
+            n_batches, nbytes, n = n_batches + 1, 0, 0
+        nbytes, n = nbytes + ln, n + 1
+    return n_batches + (1 if n else 0)
+
+
+_batch_file = {}
+
+
+def batch_file_workload():
+    """Four queries, one per word width and a second 32-bit one, and reads for
+    3,000-byte batches: 150-base reads, one read of exactly the batch size, a
+    20,000-base read (it grows an empty slot of 3000 + 750 + 4096 bytes), more
+    short reads and a 20,000-base read as the last record.  Copies of the
+    queries, some with one substitution, lie in every kind of read."""
+    if not _batch_file:
+        rng = np.random.default_rng(58)
+        a = np.frombuffer(b"ACGT", np.uint8)
+        queries = [bytes(rng.choice(a, m)) for m in (21, 33, 65, 100)]
+
+        def long_read(n):
+            T = bytearray(rng.choice(a, n).tobytes())
+            for j, at in enumerate(range(50, n - 200, max(n // 7, 300))):
+                q = bytearray(queries[j % 4])
+                if j % 2:
+                    q[len(q) // 2] = ord("A") if q[len(q) // 2] != ord("A") else ord("C")
+                T[at:at + len(q)] = q
+            return bytes(T)
+
+        reads = (planted(rng, queries, 30, 150, b"ACGT", min_len=150) + [long_read(3000), long_read(20000)]
+                 + planted(rng, queries, 30, 150, b"ACGT", min_len=150) + [long_read(20000)])
+        _batch_file.update(queries=queries, reads=reads, st=Statement(queries, reads))
+    return _batch_file["queries"], _batch_file["reads"], _batch_file["st"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("e", [0, 1])
+def test_count_file_small_batches_and_slot_growth(e, tmp_path, monkeypatch):
+    """vc_ed_count_file through the batch writer it shares with vc_count_file,
+    with VAFC_BATCH_BYTES=3000: the file is split into many batches, two of
+    them one long read in a slot grown for it, the last of these flushed at
+    the end of the file."""
+    import vafc
+    queries, reads, st = batch_file_workload()
+    lens = [len(r) for r in reads]
+    assert lens[30:32] == [3000, 20000] and lens[-1] == 20000 and set(lens) == {150, 3000, 20000}
+    fq = tmp_path / "r.fq"
+    fq.write_bytes(b"".join(b"@r%d\n%s\n+\n%s\n" % (i, r, b"I" * len(r)) for i, r in enumerate(reads)))
+    monkeypatch.setenv("VAFC_BATCH_BYTES", "3000")
+    ed = vafc.EdCounter(queries=queries, max_edit=e)
+    try:
+        fs = ed.count_file(str(fq))
+        got = ed.finish()
+    finally:
+        ed.close()
+    want = st.counts(e)
+    assert np.array_equal(got, want), (got, want)
+    assert int(want.min()) > 0
+    assert (fs.seqs, fs.bases) == (len(reads), sum(lens))
+    n_batches = batches_of(lens, 3000, 1 << 18)
+    assert n_batches == 7 and fs.blocks == n_batches      # 20 reads of 150 bases fill a batch
+
+
+@pytest.mark.gpu
+def test_count_device_side_stream_after_reset():
+    """vc_ed_count_device on a torch side stream right after a vc_ed_reset on
+    the handle's own stream, which is still busy with an earlier batch, and no
+    host synchronisation in between: the reset comes first, and vc_ed_finish
+    sees the launch.  The counts equal the same reads through count_block."""
+    import torch
+    import vafc
+    rng = np.random.default_rng(59)
+    a = np.frombuffer(b"ACGT", np.uint8)
+    queries = [bytes(rng.choice(a, m)) for m in (21, 33, 65, 100)]
+    reads = planted(rng, queries, 2000, 150, b"ACGT", min_len=100)
+    blob, offs, lens = pack(reads)
+    dev = torch.device("cuda", 0)
+    d_seq = torch.from_numpy(blob.copy()).to(dev)
+    d_offs = torch.from_numpy(offs.astype(np.int64)).to(dev)
+    d_lens = torch.from_numpy(lens.astype(np.int32)).to(dev)
+    side = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()
+    ed = vafc.EdCounter(queries=queries, max_edit=1)
+    try:
+        ed.count_block(blob, offs, lens)
+        want = ed.finish().copy()
+        assert int(want.min()) > 0
+        ed.count_block(blob, offs, lens)      # queued on the handle's stream, to be reset
+        ed.reset()
+        ed.count_device(d_seq.data_ptr(), blob.size, d_offs.data_ptr(), d_lens.data_ptr(), lens.size,
+                        side.cuda_stream)
+        got = ed.finish()
+    finally:
+        ed.close()
+    assert np.array_equal(got, want)
+
+
 @pytest.mark.gpu
 def test_exact_search_is_the_forward_share_of_the_kmer_counter(tmp_path):
     """-e 0 counts the exact forward occurrences: with distinct, non-palindromic

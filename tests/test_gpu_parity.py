@@ -385,6 +385,66 @@ def test_count_file_equals_oracle_file_pass(tmp_path):
     assert np.array_equal(got, want[: 2 * orc.n_patterns])
 
 
+def batches_of(lens, limit, max_reads):
+    """How many batches the file pass's writer submits (csrc/vafc_stage.h): a
+    batch is closed by the read that would take it past `limit` bytes or
+    `max_reads` reads; a longer read is a batch of its own."""
+    n_batches, nbytes, n = 0, 0, 0
+    for ln in lens:
+        if n and (nbytes + ln > limit or n >= max_reads):
+            n_batches, nbytes, n = n_batches + 1, 0, 0
+        nbytes, n = nbytes + ln, n + 1
+    return n_batches + (1 if n else 0)
+
+
+@pytest.mark.parametrize("shards", [1, 2])
+def test_count_file_small_batches_and_slot_growth(shards, tmp_path, monkeypatch):
+    """The sequential file pass (a plain file under 32 MB) with 3,000-byte
+    batches, so that its pinned slots (3000 + 750 + 4096 bytes) are smaller
+    than the file's long reads: 150-base reads, one read of exactly the batch
+    size, a 20,000-base read that grows an empty slot, more short reads, and a
+    20,000-base read as the last record, so that the final flush ships a grown
+    slot.  One shard, and two shards taking the batches in turn."""
+    import vafc
+    import vafc_synth as S
+    import oracle as O
+    panel = S.make_panel(S.synthetic_bed(3000))
+    pat = str(tmp_path / "p.txt")
+    panel.write_patterns(pat, 21)
+    rows = S.gen_reads(panel, 40 + 20 + 134 + 40 + 134, f_snp=0.8)
+    cut = np.cumsum([0, 40, 20, 134, 40, 134])
+    part = [rows[a:b] for a, b in zip(cut[:-1], cut[1:])]
+    reads = ([r.tobytes() for r in part[0]] + [part[1].tobytes()] + [part[2].reshape(-1)[:20000].tobytes()]
+             + [r.tobytes() for r in part[3]] + [part[4].reshape(-1)[:20000].tobytes()])
+    lens = [len(r) for r in reads]
+    assert lens[40:42] == [3000, 20000] and lens[-1] == 20000 and len(reads) == 83
+    fq = str(tmp_path / "r.fq")
+    with open(fq, "wb") as fp:
+        for i, r in enumerate(reads):
+            fp.write(b"@r%d\n%s\n+\n%s\n" % (i, r, b"I" * len(r)))
+    assert os.path.getsize(fq) < (32 << 20)
+    orc = O.Oracle(21, pattern_fn=pat)
+    want = np.zeros(2 * orc.n_patterns + 2, np.uint32)
+    rc, bases, seqs, km_want = orc.count_file(fq, 10_000_000, want)
+    assert rc == 0 and (bases, seqs) == (sum(lens), len(reads))
+    monkeypatch.setenv("VAFC_BATCH_BYTES", "3000")
+    db = vafc.load_patterns(pat)
+    m = vafc.create_combined_kmer_map(db, 21, devices=[0] * shards if shards > 1 else None)
+    try:
+        st = m.count_file(fq, 10_000_000, 4)
+        got, km = m.finish()
+        dealt = [b for _, b in m.shards()]
+    finally:
+        m.close()
+    assert (st.bases, st.seqs) == (bases, seqs)
+    assert km == km_want
+    assert np.array_equal(got, want[: 2 * orc.n_patterns])
+    assert int(got.sum()) > 0
+    n_batches = batches_of(lens, 3000, 3000 // 64)
+    assert n_batches == 7      # 20 reads of 150 bases fill a batch; each long read is one
+    assert sum(dealt) == n_batches and max(dealt) - min(dealt) <= 1
+
+
 @pytest.mark.parametrize("world,piece", [(3, 1 << 20), (5, 4_000_037), (2, 0)])
 def test_count_file_ranges_chain_to_whole_file(world, piece, tmp_path, monkeypatch):
     """vc_count_file_range over a 120k-read FASTQ (~45 MB) cut into `world`
@@ -627,6 +687,40 @@ def test_count_device_default_stream_order(torch_dev, shards):
         assert km == km_want and np.array_equal(got, want)
         assert int(want.astype(np.uint64).sum()) > 1000
     m.close()
+
+
+def test_count_device_side_stream_after_reset(torch_dev):
+    """vc_count_device on a torch side stream right after a vc_reset on the
+    counter's own stream, which is still busy with an earlier batch, and no
+    host synchronisation in between: the reset comes first, and vc_finish sees
+    the launch.  The counts equal the same reads through count_block."""
+    import torch
+    import vafc
+    import vafc_synth as S
+    import tempfile
+    panel = S.make_panel(S.synthetic_bed(3000))
+    with tempfile.TemporaryDirectory() as d:
+        pat = os.path.join(d, "p.txt")
+        panel.write_patterns(pat, 21)
+        db = vafc.load_patterns(pat)
+    seq, offs, lens = S.pack_reads(S.gen_reads(panel, 2000, f_snp=0.8))
+    d_seq = torch.from_numpy(seq).to(torch_dev)
+    d_offs = torch.from_numpy(offs.astype(np.int64)).to(torch_dev)
+    d_lens = torch.from_numpy(lens.astype(np.int32)).to(torch_dev)
+    side = torch.cuda.Stream(device=torch_dev)
+    torch.cuda.synchronize()
+    m = vafc.create_combined_kmer_map(db, 21)
+    try:
+        m.count_block(seq, offs, lens)
+        want, km_want = m.finish()
+        assert int(want.sum()) > 0 and km_want > 0
+        m.count_block(seq, offs, lens)      # queued on the counter's stream, to be reset
+        m.reset()
+        m.count_device(d_seq.data_ptr(), seq.size, d_offs.data_ptr(), d_lens.data_ptr(), lens.size, side.cuda_stream)
+        got, km = m.finish()
+    finally:
+        m.close()
+    assert km == km_want and np.array_equal(got, want)
 
 
 def test_c4_full_size_sharded(torch_dev):

@@ -1,5 +1,5 @@
 // pinned_copy.cpp -- host write rate into the staging buffers the ingest path
-// uses (tools only): 150-byte records copied one by one, as BatchWriter::add
+// uses (tools only): 150-byte records copied one by one, as VcBatchWriter::add
 // does, into hipHostMalloc memory (default, non-coherent) vs malloc'd memory.
 //   hipcc -O3 -o tools/pinned_copy tools/pinned_copy.cpp && tools/pinned_copy
 #include <hip/hip_runtime.h>
