@@ -578,6 +578,137 @@ int vc_ed_kernel_ms(vc_ed *ed, float *ms);
 int vc_ed_count_file(vc_ed *ed, const char *path, int n_threads, vc_file_stats *st);
 
 /* ------------------------------------------------------------------ */
+/* bam-vaf-counter: ref/alt base counts at SNP positions from BAM      */
+/* (bam-vaf-counter.c; record rules of htslib's sam.c bam_read1)       */
+/* ------------------------------------------------------------------ */
+
+/* The contract, read from bam-vaf-counter.c and htslib and pinned by the
+ * goldens of tests/golden/bam:
+ *
+ * 1. Patterns and tids.  Row i of vc_patterns_load has chr, pos = start, ref
+ *    and alt (one byte each, compared exactly: lower case never matches).  A
+ *    row's tid is the index of chr in the FIRST input file's reference list
+ *    and is used for every later file.  A row whose chr is absent gets a
+ *    warning line and never counts.  Duplicate positions warn, and every such
+ *    row counts on its own.
+ * 2. A record with flag 0x4, 0x200 or 0x400 is skipped (secondary and
+ *    supplementary records count).  A record with tid < 0 overlaps nothing.
+ * 3. The CIGAR walk.  For a record at (tid, pos), end = pos + rlen, rlen the
+ *    reference length of its CIGAR (ops M, D, N, =, X), or 1 if that is 0.
+ *    Every row with that tid and pos <= row.pos < end is looked at; the walk
+ *    starts at cur = pos, rp = 0.  M, = and X of length L: if cur <= row.pos <
+ *    cur + L the base is "=ACMGRSVTWYHKDBN"[nibble rp + row.pos - cur]; base
+ *    == ref adds w to ref_count, else base == alt adds w to alt_count; either
+ *    way the walk stops.  Otherwise cur and rp advance by L.  I and S advance
+ *    rp.  D and N: inside, the walk stops with no count; otherwise cur
+ *    advances.  H, P and op codes 9..15 do nothing.  ref == alt counts as ref.
+ * 4. Counts are uint32 sums over all records of all files and wrap.
+ * 5. Without a usable index w = 1.
+ * 6. With an index (the first existing of <fn>.csi, <fn minus its last
+ *    extension>.csi, <fn>.bai, <fn minus its last extension>.bai, if it
+ *    carries the BAI\1 magic or is BGZF whose text starts CSI\1) the
+ *    reference fetches every merged region in turn and counts all overlapping
+ *    rows of every record fetched, so w = the number of merged regions [s, e)
+ *    with region tid == tid, pos < e and end > s.  Regions (build_regions,
+ *    :124-175): one [pos, pos + 1) per row, sorted by strcmp(chr) then start,
+ *    merged while prev.end >= next.start; a region's tid is looked up in THIS
+ *    file's header, regions on an absent chromosome warn and are skipped.  The
+ *    whole file is read and w applied; nothing seeks.
+ * 7. What ends a file's records, keeping those before, silently and with exit
+ *    code 0.  A BGZF block that is truncated, does not inflate or fails its
+ *    CRC-32 / ISIZE, and a record cut off by the end of the data, end them
+ *    (htslib's BGZF error is sticky).  A failure of one record (sam.c
+ *    bam_read1) does so only where the reference's reading loop (:380-397)
+ *    and kt_pipeline's two workers make it: records are read in batches of
+ *    1,000, a failed read closes the batch, and the file ends at the second
+ *    batch that closes empty (each worker leaves at its first).  So a
+ *    block_size < 32, fields that do not fit the block_size (or l_read_name
+ *    = 0, l_seq < 0), malformed aux data in front of a CG tag that is looked
+ *    for, and a record with n_cigar > 0, l_seq > 0, flag 0x4 clear and a
+ *    CIGAR query length != l_seq drop that record, and reading goes on behind
+ *    the bytes htslib has consumed: the 4 of the block_size word, the 36 up
+ *    to the fixed fields, or the whole record.  The file ends where such a
+ *    failure is, for the second time, the first read of its batch (right
+ *    after 1,000 good records or after another failure): three failures in a
+ *    row always end it.  A missing EOF block ends nothing.
+ * 8. Deviations: BGZF-compressed BAM only; a base index at or past l_seq
+ *    counts nothing (so l_seq == 0 with a CIGAR counts nothing); a record in
+ *    the CG:B,I long-CIGAR convention is counted with its real CIGAR, as
+ *    htslib moves it in; htslib's own [E::/[W:: lines are not reproduced. */
+
+/* One record as the kernels read it: its n_cigar CIGAR words (BAM encoding,
+ * len << 4 | op) at data + off, off a multiple of 4, followed by its (l_seq +
+ * 1) / 2 bytes of packed 4-bit bases. */
+typedef struct {
+	int32_t tid, pos;
+	uint32_t flag, n_cigar, l_seq;
+	uint32_t reserved;     /* 0 */
+	uint64_t off;
+} vc_bam_rec;
+
+typedef struct vc_bam vc_bam;
+typedef struct vc_bam_file vc_bam_file;
+
+/* Kinds of input, vc_bam_probe: only VC_BAM_BGZF is read. */
+enum { VC_BAM_BGZF = 0, VC_BAM_SAM = 1, VC_BAM_CRAM = 2, VC_BAM_RAW = 3, VC_BAM_GZIP = 4, VC_BAM_BGZF_OTHER = 5 };
+/* What a file is by its first bytes; VC_EIO if it cannot be opened. */
+int vc_bam_probe(const char *path, int *kind);
+const char *vc_bam_kind_name(int kind);
+
+/* Host reader (zlib and threads, no GPU): the header and every record of a
+ * BGZF BAM under items 7 and 8, as descriptors into one data buffer.  VC_EIO:
+ * cannot be opened; VC_EINVAL: not BGZF BAM, or the header cannot be read
+ * (the file object is still returned with no references when it opened).
+ * vc_bam_read_header stops behind the header (sam_hdr_read of main, :512-527). */
+int vc_bam_read_file(const char *path, int n_threads, vc_bam_file **out);
+int vc_bam_read_header(const char *path, vc_bam_file **out);
+int vc_bam_file_refs(const vc_bam_file *f);
+const char *vc_bam_file_ref_name(const vc_bam_file *f, int i);
+uint64_t vc_bam_file_records(const vc_bam_file *f, const vc_bam_rec **recs, const uint8_t **data, uint64_t *data_bytes);
+void vc_bam_file_free(vc_bam_file *f);
+/* The index file item 6 finds for `path` (a copy into buf), 1 if it carries a
+ * usable magic, 0 if there is none or it does not. */
+int vc_bam_index_usable(const char *path, char *buf, size_t buf_len);
+/* build_regions (bam-vaf-counter.c:124-175): row indices whose (chr, start)
+ * open a merged region, its end in ends[]; both arrays hold
+ * vc_patterns_count entries, the return value is the number of regions. */
+int vc_bam_build_regions(const vc_patterns *db, int32_t *first_row, int32_t *ends);
+
+/* A counter for the rows of db, their tids from ref_names[0..n_refs) (the
+ * first file's header, create_snp_map :187-215, whose two warnings are
+ * written to stderr).  Counts layout [2 * n_patterns] as vc_ed_create. */
+int vc_bam_create(vc_bam **out, const vc_patterns *db, const char *const *ref_names, int n_refs, int device);
+void vc_bam_destroy(vc_bam *b);
+/* The merged regions of the file being counted, for item 6's weights: tids in
+ * that file's header, n = 0 for item 5 (all weights 1, the state after
+ * create).  Asynchronous on the handle's stream; holds for later count calls. */
+int vc_bam_set_regions(vc_bam *b, const int32_t *tid, const int32_t *start, const int32_t *end, size_t n);
+/* Count one block of host-resident records (staged through pinned memory,
+ * asynchronous, accumulating, buffers reusable on return). */
+int vc_bam_count_block(vc_bam *b, const vc_bam_rec *recs, uint64_t n_recs, const uint8_t *data, size_t data_bytes);
+/* The same for HBM-resident records on `stream`, with vc_count_device's
+ * ordering contract.  data_bytes bounds every device read: a descriptor that
+ * points outside it (or off a 4-byte boundary) is not followed and makes
+ * vc_bam_finish return VC_EINVAL. */
+int vc_bam_count_device(vc_bam *b, const vc_bam_rec *d_recs, uint64_t n_recs, const uint8_t *d_data,
+                        size_t data_bytes, void *stream);
+int vc_bam_finish(vc_bam *b, uint32_t *counts);
+int vc_bam_reset(vc_bam *b);
+int vc_bam_set_counts(vc_bam *b, const uint32_t *counts);
+/* Records of more than `ops` CIGAR operations get a wave each instead of a
+ * lane (default 64; 0: every record with a CIGAR, UINT32_MAX: none).  The
+ * counts do not depend on it. */
+int vc_bam_set_long_threshold(vc_bam *b, uint32_t ops);
+int vc_bam_kernel_ms(vc_bam *b, float *ms);
+/* count_bam_variants (bam-vaf-counter.c:417-470) for one file: its own stderr
+ * lines, the regions and weights of items 5 and 6 from this file's header and
+ * index, every record through the kernels.  n_threads inflate BGZF blocks.
+ * VC_EIO: cannot be opened; VC_EINVAL: not BGZF BAM or no readable header
+ * (nothing counted in both cases).  st: seqs = records, bases = sum of l_seq,
+ * blocks = batches. */
+int vc_bam_count_file(vc_bam *b, const char *path, int n_threads, vc_file_stats *st);
+
+/* ------------------------------------------------------------------ */
 /* Synthetic workload (bench / tests): the generator of vafc_synth.py,  */
 /* evaluated on the device.                                            */
 /* ------------------------------------------------------------------ */

@@ -1,0 +1,618 @@
+// vafc_bam.hip -- bam-vaf-counter on the device (vc_bam_* of include/vafc.h):
+// the reference's worker_check_positions / count_base_at_position
+// (bam-vaf-counter.c:238-318), which tests every pattern row against every
+// record, as a search in the rows sorted by (tid, pos).
+//
+//   rows          (tid, pos) keys ascending, beside each the row's index in
+//                 the pattern file and its ref / alt bytes; small enough to
+//                 stay in L2
+//   short kernel  one lane per record: lower bound of (tid, pos), then one
+//                 merged walk of the CIGAR and the rows, both ascending in
+//                 reference position
+//   long kernel   records of more CIGAR ops than the threshold are listed by
+//                 the short kernel and get a wave each: 64 ops at a time, a
+//                 wave-wide scan of the reference and query advances gives
+//                 every lane its op's interval, and each M/=/X lane searches
+//                 the rows inside its own
+//   weights       item 6 of the contract: the number of merged regions a
+//                 record overlaps, from two sorted key arrays
+//
+// Every global read is bounded: rows and regions by their counts, descriptors
+// by n_recs, and a record's CIGAR and bases by data_bytes before the first of
+// them is read (a descriptor that fails sets flags bit 0 and is not followed).
+// CIGAR words are read as aligned dwords (offsets are multiples of 4), bases
+// as bytes.
+//
+// Nothing here counts on the CPU: any HIP failure is returned as VC_EHIP.
+#include <hip/hip_runtime.h>
+
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <new>
+#include <string>
+#include <unordered_map>
+#include <unordered_set>
+#include <vector>
+
+#include "vafc.h"
+#include "vafc_bam.h"
+#include "vafc_stage.h"
+
+namespace {
+
+struct VcBamArgs {
+	const vc_bam_rec *recs;
+	uint64_t n_recs;
+	const uint8_t *data;
+	uint64_t data_bytes;
+	const uint64_t *row_key;     // [n_rows] bam_key(tid, pos), ascending
+	const uint2 *row_info;       // [n_rows] x: row index in the pattern file, y: ref | alt << 8
+	uint32_t n_rows;
+	const uint64_t *reg_s;       // [n_reg] keys of the region starts, ascending
+	const uint64_t *reg_e;       // [n_reg] keys of the region ends, ascending
+	uint32_t n_reg;              // 0: every weight is 1
+	uint32_t long_thr;
+	uint32_t *long_list;         // [n_recs] records left to the long kernel
+	uint32_t *long_n;
+	uint32_t *counts;
+	uint32_t *flags;             // bit 0: a descriptor points outside data
+};
+
+const uint32_t BAM_SKIP_FLAGS = 0x4u | 0x200u | 0x400u;
+const int BAM_BLOCK = 256;
+const int64_t BAM_POS_END = (int64_t)1 << 31;   // one past the largest row position
+
+// (tid, x) as one sortable word, tid >= 0 and x in [-2^31, 2^31].
+__host__ __device__ inline uint64_t bam_key(int32_t tid, int64_t x)
+{
+	return ((uint64_t)(uint32_t)tid << 33) + (uint64_t)(x + BAM_POS_END);
+}
+
+__device__ inline int64_t bam_key_pos(uint64_t key) { return (int64_t)(key & (((uint64_t)1 << 33) - 1)) - BAM_POS_END; }
+
+// First i with a[i] >= key.
+__device__ inline uint32_t bam_lower(const uint64_t *a, uint32_t n, uint64_t key)
+{
+	uint32_t lo = 0, hi = n;
+	while (lo < hi) {
+		const uint32_t mid = lo + ((hi - lo) >> 1);
+		if (a[mid] < key) lo = mid + 1;
+		else hi = mid;
+	}
+	return lo;
+}
+
+__device__ inline bool bam_ref_op(uint32_t op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
+__device__ inline bool bam_query_op(uint32_t op) { return op == 0 || op == 1 || op == 4 || op == 7 || op == 8; }
+__device__ inline bool bam_match_op(uint32_t op) { return op == 0 || op == 7 || op == 8; }
+
+// The record's CIGAR and bases lie inside data, on a 4-byte boundary.
+__device__ inline bool bam_in_bounds(const vc_bam_rec &r, uint64_t data_bytes)
+{
+	const uint64_t need = 4 * (uint64_t)r.n_cigar + (((uint64_t)r.l_seq + 1) >> 1);
+	return (r.off & 3) == 0 && r.off <= data_bytes && need <= data_bytes - r.off;
+}
+
+// Item 6: merged regions [s, e) of this tid with s < end and e > pos.
+__device__ inline uint32_t bam_weight(const VcBamArgs &A, int32_t tid, int64_t pos, int64_t end)
+{
+	if (A.n_reg == 0) return 1;
+	const uint32_t starts_below = bam_lower(A.reg_s, A.n_reg, bam_key(tid, end));
+	const uint32_t ends_upto = bam_lower(A.reg_e, A.n_reg, bam_key(tid, pos) + 1);
+	return starts_below - ends_upto;
+}
+
+// Row j against base qi of the record: ref first, else alt.
+__device__ inline void bam_hit(const VcBamArgs &A, uint32_t j, const uint8_t *seq, uint64_t qi, uint32_t l_seq, uint32_t w)
+{
+	if (qi >= l_seq) return;
+	const uint32_t b = seq[qi >> 1];
+	const uint32_t nib = (qi & 1) ? (b & 15u) : (b >> 4);
+	const uint32_t base = (uint32_t)(uint8_t) "=ACMGRSVTWYHKDBN"[nib];
+	const uint2 info = A.row_info[j];
+	const uint32_t ref = info.y & 255u, alt = (info.y >> 8) & 255u;
+	if (base == ref) atomicAdd(&A.counts[2 * (size_t)info.x], w);
+	else if (base == alt) atomicAdd(&A.counts[2 * (size_t)info.x + 1], w);
+}
+
+__global__ void __launch_bounds__(BAM_BLOCK) bam_short_kernel(VcBamArgs A)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * BAM_BLOCK + threadIdx.x;
+	if (i >= A.n_recs) return;
+	const vc_bam_rec r = A.recs[i];
+	if (!bam_in_bounds(r, A.data_bytes)) {
+		atomicOr(A.flags, 1u);
+		return;
+	}
+	if ((r.flag & BAM_SKIP_FLAGS) || r.tid < 0 || r.n_cigar == 0) return;
+	if (r.n_cigar > A.long_thr) {
+		A.long_list[atomicAdd(A.long_n, 1u)] = (uint32_t)i;
+		return;
+	}
+	const uint64_t tid_end = bam_key(r.tid, BAM_POS_END);
+	uint32_t j = bam_lower(A.row_key, A.n_rows, bam_key(r.tid, r.pos));
+	if (j >= A.n_rows || A.row_key[j] > tid_end) return;   // most records: no row at or after them
+	const uint32_t *cig = reinterpret_cast<const uint32_t *>(A.data + r.off);
+	const uint8_t *seq = A.data + r.off + 4 * (size_t)r.n_cigar;
+	int64_t rlen = 0;
+	for (uint32_t k = 0; k < r.n_cigar; ++k) {
+		const uint32_t c = cig[k];
+		if (bam_ref_op(c & 15u)) rlen += c >> 4;
+	}
+	int64_t end = (int64_t)r.pos + (rlen ? rlen : 1);
+	if (end > BAM_POS_END) end = BAM_POS_END;
+	const uint64_t end_key = bam_key(r.tid, end);
+	if (A.row_key[j] >= end_key) return;
+	const uint32_t w = bam_weight(A, r.tid, r.pos, end);
+	if (w == 0) return;
+	// the merged walk: op k covers [cur, cur + L) when it consumes the reference
+	uint32_t k = 0;
+	int64_t cur = r.pos;
+	uint64_t rp = 0;
+	for (; j < A.n_rows; ++j) {
+		const uint64_t key = A.row_key[j];
+		if (key >= end_key) break;
+		const int64_t p = bam_key_pos(key);
+		uint32_t op = 0, len = 0;
+		for (; k < r.n_cigar; ++k) {
+			const uint32_t c = cig[k];
+			op = c & 15u;
+			len = c >> 4;
+			if (bam_ref_op(op)) {
+				if (p < cur + (int64_t)len) break;
+				cur += len;
+			}
+			if (bam_query_op(op)) rp += len;
+		}
+		if (k >= r.n_cigar) break;   // no op left covers this row or a later one
+		if (bam_match_op(op)) bam_hit(A, j, seq, rp + (uint64_t)(p - cur), r.l_seq, w);
+	}
+}
+
+// Inclusive scan over the wave's 64 lanes.
+__device__ inline uint64_t bam_wave_scan(uint64_t v, int lane)
+{
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) {
+		const uint64_t u = __shfl_up((unsigned long long)v, d, 64);
+		if (lane >= d) v += u;
+	}
+	return v;
+}
+
+__global__ void __launch_bounds__(BAM_BLOCK) bam_long_kernel(VcBamArgs A)
+{
+	const int lane = threadIdx.x & 63;
+	const uint32_t waves = gridDim.x * (BAM_BLOCK / 64);
+	const uint32_t n_long = *A.long_n;
+	for (uint32_t e = blockIdx.x * (BAM_BLOCK / 64) + (threadIdx.x >> 6); e < n_long; e += waves) {
+		const vc_bam_rec r = A.recs[A.long_list[e]];   // listed by the short kernel: in bounds, not skipped
+		const uint32_t *cig = reinterpret_cast<const uint32_t *>(A.data + r.off);
+		const uint8_t *seq = A.data + r.off + 4 * (size_t)r.n_cigar;
+		uint32_t w = 1;
+		if (A.n_reg) {
+			uint64_t rl = 0;
+			for (uint32_t k = (uint32_t)lane; k < r.n_cigar; k += 64) {
+				const uint32_t c = cig[k];
+				if (bam_ref_op(c & 15u)) rl += c >> 4;
+			}
+#pragma unroll
+			for (int d = 32; d > 0; d >>= 1) rl += __shfl_xor((unsigned long long)rl, d, 64);
+			int64_t end = (int64_t)r.pos + (rl ? (int64_t)rl : 1);
+			if (end > BAM_POS_END) end = BAM_POS_END;
+			w = bam_weight(A, r.tid, r.pos, end);
+			if (w == 0) continue;   // the same in every lane
+		}
+		int64_t base_cur = r.pos;
+		uint64_t base_rp = 0;
+		for (uint32_t g = 0; g < r.n_cigar; g += 64) {
+			const uint32_t k = g + (uint32_t)lane;
+			const uint32_t c = k < r.n_cigar ? cig[k] : 0xFu;   // past the end: a reserved op, it does nothing
+			const uint32_t op = c & 15u, len = c >> 4;
+			const uint64_t radv = bam_ref_op(op) ? len : 0, qadv = bam_query_op(op) ? len : 0;
+			const uint64_t rsum = bam_wave_scan(radv, lane), qsum = bam_wave_scan(qadv, lane);
+			const int64_t cur = base_cur + (int64_t)(rsum - radv);
+			const uint64_t rp = base_rp + (qsum - qadv);
+			if (bam_match_op(op) && len > 0 && cur < BAM_POS_END) {
+				int64_t hi = cur + (int64_t)len;
+				if (hi > BAM_POS_END) hi = BAM_POS_END;
+				const uint64_t hi_key = bam_key(r.tid, hi);
+				for (uint32_t j = bam_lower(A.row_key, A.n_rows, bam_key(r.tid, cur)); j < A.n_rows; ++j) {
+					const uint64_t key = A.row_key[j];
+					if (key >= hi_key) break;
+					bam_hit(A, j, seq, rp + (uint64_t)(bam_key_pos(key) - cur), r.l_seq, w);
+				}
+			}
+			base_cur += (int64_t)__shfl((unsigned long long)rsum, 63, 64);
+			base_rp += __shfl((unsigned long long)qsum, 63, 64);
+		}
+	}
+}
+
+// records and data bytes of one batch of vc_bam_count_file ($VAFC_BATCH_BYTES: vc_batch_bytes)
+const size_t BAM_BATCH_BYTES = (size_t)32 << 20;
+const size_t BAM_BATCH_RECS = (size_t)1 << 19;
+
+} // namespace
+
+struct vc_bam {
+	int dev = 0;
+	int n_cu = 256;
+	uint32_t n_pat = 0, n_rows = 0;
+	hipStream_t st = nullptr;
+	uint64_t *d_row_key = nullptr;
+	uint2 *d_row_info = nullptr;
+	uint32_t *d_counts = nullptr, *d_flags = nullptr;
+	uint64_t *d_reg_s = nullptr, *d_reg_e = nullptr;
+	uint32_t n_reg = 0;
+	size_t reg_cap = 0;
+	uint32_t *d_long_list = nullptr, *d_long_n = nullptr;
+	uint64_t long_cap = 0;
+	uint32_t long_thr = 64;
+	VcStager stage;
+	VcStreamBridge bridge;
+	hipEvent_t t0 = nullptr, t1 = nullptr;
+	bool timed = false;
+	// the rows as build_regions sees them: merged regions by chromosome name
+	std::vector<std::string> reg_chr;
+	std::vector<int32_t> reg_start, reg_end;
+};
+
+namespace {
+
+int launch(vc_bam *c, const vc_bam_rec *d_recs, uint64_t n_recs, const uint8_t *d_data, size_t data_bytes, hipStream_t st)
+{
+	if (n_recs == 0) return VC_OK;
+	if (n_recs > 0xFFFFFFFFull || ((uintptr_t)d_recs & 7) || ((uintptr_t)d_data & 3)) return VC_EINVAL;
+	if (n_recs > c->long_cap) {   // hipFree waits for the kernels that still use the old list
+		if (c->d_long_list) HIPCK(hipFree(c->d_long_list));
+		c->d_long_list = nullptr;
+		c->long_cap = 0;
+		const uint64_t cap = n_recs + n_recs / 4 + 1024;
+		HIPCK(hipMalloc((void **)&c->d_long_list, cap * sizeof(uint32_t)));
+		c->long_cap = cap;
+	}
+	VcBamArgs A;
+	A.recs = d_recs;
+	A.n_recs = n_recs;
+	A.data = d_data;
+	A.data_bytes = data_bytes;
+	A.row_key = c->d_row_key;
+	A.row_info = c->d_row_info;
+	A.n_rows = c->n_rows;
+	A.reg_s = c->d_reg_s;
+	A.reg_e = c->d_reg_e;
+	A.n_reg = c->n_reg;
+	A.long_thr = c->long_thr;
+	A.long_list = c->d_long_list;
+	A.long_n = c->d_long_n;
+	A.counts = c->d_counts;
+	A.flags = c->d_flags;
+	HIPCK(hipMemsetAsync(c->d_long_n, 0, sizeof(uint32_t), st));
+	HIPCK(hipEventRecord(c->t0, st));
+	const unsigned grid = (unsigned)((n_recs + BAM_BLOCK - 1) / BAM_BLOCK);
+	hipLaunchKernelGGL(bam_short_kernel, dim3(grid), dim3(BAM_BLOCK), 0, st, A);
+	HIPCK(hipGetLastError());
+	// the list's length is known on the device only: a fixed grid of waves walks it
+	uint64_t lgrid = (uint64_t)c->n_cu * 2;
+	if (lgrid > (n_recs + 3) / 4) lgrid = (n_recs + 3) / 4;
+	hipLaunchKernelGGL(bam_long_kernel, dim3((unsigned)lgrid), dim3(BAM_BLOCK), 0, st, A);
+	HIPCK(hipGetLastError());
+	HIPCK(hipEventRecord(c->t1, st));
+	c->timed = true;
+	return VC_OK;
+}
+
+} // namespace
+
+extern "C" int vc_bam_create(vc_bam **out, const vc_patterns *db, const char *const *ref_names, int n_refs, int device)
+{
+	if (!out || !db || n_refs < 0 || (n_refs && !ref_names)) return VC_EINVAL;
+	*out = nullptr;
+	const int n = vc_patterns_count(db);
+	if (n > (0x7FFFFFFF >> 1)) return VC_ETOOMANY;
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VC_ENODEV;
+	if (device < 0 || device >= ndev) return VC_EINVAL;
+	HIPCK(hipSetDevice(device));
+	vc_bam *c = new (std::nothrow) vc_bam;
+	if (!c) return VC_ENOMEM;
+	c->dev = device;
+	c->n_pat = (uint32_t)n;
+	hipDeviceProp_t prop;
+	if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
+		c->n_cu = prop.multiProcessorCount;
+
+	// create_snp_map (bam-vaf-counter.c:187-215): tids and the two warnings, in row order
+	std::unordered_map<std::string, int32_t> tid_of;
+	for (int i = 0; i < n_refs; ++i) tid_of.emplace(ref_names[i], i);
+	struct Row {
+		uint64_t key;
+		uint2 info;
+	};
+	std::vector<Row> rows;
+	std::unordered_set<uint64_t> seen;
+	for (int i = 0; i < n; ++i) {
+		const char *chr = nullptr;
+		int start = 0;
+		char ref = 0, alt = 0;
+		if (vc_pattern_fields(db, i, &chr, &start, nullptr, &ref, &alt, nullptr, nullptr) != VC_OK) {
+			delete c;
+			return VC_EINVAL;
+		}
+		const auto it = tid_of.find(chr);
+		if (it == tid_of.end()) {
+			fprintf(stderr, "Warning: chromosome %s not found in BAM header\n", chr);
+			continue;
+		}
+		if (!seen.insert(((uint64_t)(uint32_t)it->second << 32) | (uint32_t)start).second)
+			fprintf(stderr, "Warning: duplicate SNP at %s:%d\n", chr, start);
+		Row r;
+		r.key = bam_key(it->second, start);
+		r.info.x = (uint32_t)i;
+		r.info.y = (uint32_t)(uint8_t)ref | (uint32_t)(uint8_t)alt << 8;
+		rows.push_back(r);
+	}
+	std::stable_sort(rows.begin(), rows.end(), [](const Row &a, const Row &b) { return a.key < b.key; });
+	c->n_rows = (uint32_t)rows.size();
+	std::vector<uint64_t> keys(rows.size() + 1, 0);
+	std::vector<uint2> info(rows.size() + 1);
+	for (size_t i = 0; i < rows.size(); ++i) {
+		keys[i] = rows[i].key;
+		info[i] = rows[i].info;
+	}
+
+	// build_regions (:124-175), kept by name: their tids depend on each file's header
+	if (n > 0) {
+		std::vector<int32_t> first((size_t)n), ends((size_t)n);
+		const int nr = vc_bam_build_regions(db, first.data(), ends.data());
+		for (int i = 0; i < nr; ++i) {
+			const char *chr = nullptr;
+			int start = 0;
+			(void)vc_pattern_fields(db, first[(size_t)i], &chr, &start, nullptr, nullptr, nullptr, nullptr, nullptr);
+			c->reg_chr.emplace_back(chr);
+			c->reg_start.push_back(start);
+			c->reg_end.push_back(ends[(size_t)i]);
+		}
+	}
+
+#define TRY(call)                                                                                  \
+	do {                                                                                           \
+		hipError_t e_ = (call);                                                                    \
+		if (e_ != hipSuccess) {                                                                    \
+			fprintf(stderr, "[E::vafc] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_),     \
+			        __FILE__, __LINE__);                                                           \
+			vc_bam_destroy(c);                                                                     \
+			return VC_EHIP;                                                                        \
+		}                                                                                          \
+	} while (0)
+	TRY(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
+	TRY(hipMalloc((void **)&c->d_row_key, keys.size() * sizeof(uint64_t)));
+	TRY(hipMemcpy(c->d_row_key, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+	TRY(hipMalloc((void **)&c->d_row_info, info.size() * sizeof(uint2)));
+	TRY(hipMemcpy(c->d_row_info, info.data(), info.size() * sizeof(uint2), hipMemcpyHostToDevice));
+	TRY(hipMalloc((void **)&c->d_counts, (2 * (size_t)n + 2) * sizeof(uint32_t)));
+	TRY(hipMemset(c->d_counts, 0, (2 * (size_t)n + 2) * sizeof(uint32_t)));
+	TRY(hipMalloc((void **)&c->d_flags, sizeof(uint32_t)));
+	TRY(hipMemset(c->d_flags, 0, sizeof(uint32_t)));
+	TRY(hipMalloc((void **)&c->d_long_n, sizeof(uint32_t)));
+	TRY(hipMemset(c->d_long_n, 0, sizeof(uint32_t)));
+	TRY(hipEventCreate(&c->t0));
+	TRY(hipEventCreate(&c->t1));
+#undef TRY
+	if (c->stage.init() != VC_OK) {
+		vc_bam_destroy(c);
+		return VC_EHIP;
+	}
+	*out = c;
+	return VC_OK;
+}
+
+extern "C" void vc_bam_destroy(vc_bam *c)
+{
+	if (!c) return;
+	(void)hipSetDevice(c->dev);
+	if (c->st) (void)hipStreamSynchronize(c->st);
+	c->stage.destroy();
+	if (c->d_row_key) (void)hipFree(c->d_row_key);
+	if (c->d_row_info) (void)hipFree(c->d_row_info);
+	if (c->d_counts) (void)hipFree(c->d_counts);
+	if (c->d_flags) (void)hipFree(c->d_flags);
+	if (c->d_reg_s) (void)hipFree(c->d_reg_s);
+	if (c->d_reg_e) (void)hipFree(c->d_reg_e);
+	if (c->d_long_list) (void)hipFree(c->d_long_list);
+	if (c->d_long_n) (void)hipFree(c->d_long_n);
+	if (c->t0) (void)hipEventDestroy(c->t0);
+	if (c->t1) (void)hipEventDestroy(c->t1);
+	c->bridge.destroy();
+	if (c->st) (void)hipStreamDestroy(c->st);
+	delete c;
+}
+
+extern "C" int vc_bam_set_regions(vc_bam *c, const int32_t *tid, const int32_t *start, const int32_t *end, size_t n)
+{
+	if (!c || (n && (!tid || !start || !end)) || n > 0x7FFFFFFFu) return VC_EINVAL;
+	std::vector<uint64_t> s(n), e(n);
+	for (size_t i = 0; i < n; ++i) {
+		if (tid[i] < 0 || start[i] >= end[i]) return VC_EINVAL;
+		s[i] = bam_key(tid[i], start[i]);
+		e[i] = bam_key(tid[i], end[i]);
+	}
+	// each array in its own order: the weight is (starts below end) - (ends up to pos)
+	std::sort(s.begin(), s.end());
+	std::sort(e.begin(), e.end());
+	HIPCK(hipSetDevice(c->dev));
+	HIPCK(hipStreamSynchronize(c->st));   // earlier batches read the arrays about to change
+	if (n > c->reg_cap) {
+		if (c->d_reg_s) HIPCK(hipFree(c->d_reg_s));
+		if (c->d_reg_e) HIPCK(hipFree(c->d_reg_e));
+		c->d_reg_s = c->d_reg_e = nullptr;
+		c->reg_cap = 0;
+		HIPCK(hipMalloc((void **)&c->d_reg_s, n * sizeof(uint64_t)));
+		HIPCK(hipMalloc((void **)&c->d_reg_e, n * sizeof(uint64_t)));
+		c->reg_cap = n;
+	}
+	if (n) {
+		HIPCK(hipMemcpy(c->d_reg_s, s.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
+		HIPCK(hipMemcpy(c->d_reg_e, e.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
+	}
+	c->n_reg = (uint32_t)n;
+	return VC_OK;
+}
+
+extern "C" int vc_bam_count_block(vc_bam *c, const vc_bam_rec *recs, uint64_t n_recs, const uint8_t *data, size_t data_bytes)
+{
+	if (!c || (n_recs && !recs) || (data_bytes && !data)) return VC_EINVAL;
+	if (n_recs == 0) return VC_OK;
+	if (n_recs > 0xFFFFFFFFull) return VC_EINVAL;
+	HIPCK(hipSetDevice(c->dev));
+	const size_t rec_bytes = (size_t)n_recs * sizeof(vc_bam_rec), total = rec_bytes + data_bytes;
+	VcSlot *s;
+	int rc = c->stage.acquire(&s);
+	if (rc == VC_OK) rc = vc_slot_reserve(*s, total, 1);
+	if (rc != VC_OK) return rc;
+	// descriptors first, the data behind them: both keep their alignment
+	memcpy(s->h_seq, recs, rec_bytes);
+	if (data_bytes) memcpy(s->h_seq + rec_bytes, data, data_bytes);
+	return c->stage.submit(total, n_recs, c->st, [&](const VcSlot &sl) {
+		return launch(c, reinterpret_cast<const vc_bam_rec *>(sl.d_seq), n_recs, sl.d_seq + rec_bytes, data_bytes, c->st);
+	}, false);
+}
+
+extern "C" int vc_bam_count_device(vc_bam *c, const vc_bam_rec *d_recs, uint64_t n_recs, const uint8_t *d_data,
+                                   size_t data_bytes, void *stream)
+{
+	if (!c || (n_recs && !d_recs) || (data_bytes && !d_data)) return VC_EINVAL;
+	if (n_recs == 0) return VC_OK;
+	HIPCK(hipSetDevice(c->dev));
+	const hipStream_t st = stream == VC_STREAM_CTX ? c->st : (hipStream_t)stream;
+	int rc = c->bridge.enter(c->st, st);
+	if (rc == VC_OK) rc = launch(c, d_recs, n_recs, d_data, data_bytes, st);
+	if (rc == VC_OK) rc = c->bridge.leave(c->st, st);
+	return rc;
+}
+
+extern "C" int vc_bam_finish(vc_bam *c, uint32_t *counts)
+{
+	if (!c) return VC_EINVAL;
+	HIPCK(hipSetDevice(c->dev));
+	HIPCK(hipStreamSynchronize(c->st));
+	c->stage.settle();
+	uint32_t f = 0;
+	HIPCK(hipMemcpy(&f, c->d_flags, sizeof f, hipMemcpyDeviceToHost));
+	if (f & 1u) {
+		fprintf(stderr, "[E::vafc] a record descriptor points outside the data buffer: counts incomplete\n");
+		return VC_EINVAL;
+	}
+	if (counts && c->n_pat)
+		HIPCK(hipMemcpy(counts, c->d_counts, 2 * (size_t)c->n_pat * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	return VC_OK;
+}
+
+extern "C" int vc_bam_reset(vc_bam *c)
+{
+	if (!c) return VC_EINVAL;
+	HIPCK(hipSetDevice(c->dev));
+	HIPCK(hipMemsetAsync(c->d_counts, 0, (2 * (size_t)c->n_pat + 2) * sizeof(uint32_t), c->st));
+	HIPCK(hipMemsetAsync(c->d_flags, 0, sizeof(uint32_t), c->st));
+	return VC_OK;
+}
+
+extern "C" int vc_bam_set_counts(vc_bam *c, const uint32_t *counts)
+{
+	if (!c || (c->n_pat && !counts)) return VC_EINVAL;
+	HIPCK(hipSetDevice(c->dev));
+	if (c->n_pat) {
+		// pageable source: the copy has left the caller's buffer on return
+		HIPCK(hipMemcpyAsync(c->d_counts, counts, 2 * (size_t)c->n_pat * sizeof(uint32_t), hipMemcpyHostToDevice, c->st));
+		HIPCK(hipStreamSynchronize(c->st));
+	}
+	return VC_OK;
+}
+
+extern "C" int vc_bam_set_long_threshold(vc_bam *c, uint32_t ops)
+{
+	if (!c) return VC_EINVAL;
+	c->long_thr = ops;
+	return VC_OK;
+}
+
+extern "C" int vc_bam_kernel_ms(vc_bam *c, float *ms)
+{
+	if (!c || !ms || !c->timed) return VC_EINVAL;
+	HIPCK(hipEventSynchronize(c->t1));
+	HIPCK(hipEventElapsedTime(ms, c->t0, c->t1));
+	return VC_OK;
+}
+
+extern "C" int vc_bam_count_file(vc_bam *c, const char *path, int n_threads, vc_file_stats *stats)
+{
+	if (!c || !path) return VC_EINVAL;
+	const double t0 = vc_now();
+	vc_file_stats st;
+	memset(&st, 0, sizeof st);
+	if (stats) *stats = st;
+	VcBamReader rd;
+	int rc = rd.open(path, n_threads);
+	if (rc == VC_EIO) {
+		fprintf(stderr, "Error: failed to open BAM file: %s\n", path);
+		return rc;
+	}
+	if (rc != VC_OK) {
+		int kind = VC_BAM_BGZF;
+		if (vc_bam_probe(path, &kind) == VC_OK && kind == VC_BAM_BGZF) fprintf(stderr, "Error: failed to read BAM header\n");
+		return rc;
+	}
+	// count_bam_variants :436-458: regions are used only beside an index
+	const bool have_regions = !c->reg_chr.empty();
+	const bool have_index = vc_bam_index_usable(path, nullptr, 0) != 0;
+	std::vector<int32_t> tid, start, end;
+	if (!have_index || !have_regions) {
+		if (!have_index)
+			fprintf(stderr, "[M::%s] Warning: failed to load BAM index for %s, processing all reads\n", "count_bam_variants", path);
+		if (!have_regions)
+			fprintf(stderr, "[M::%s] Warning: no target regions available, processing all reads\n", "count_bam_variants");
+	} else {
+		fprintf(stderr, "[M::%s] Using indexed access to fetch reads from %d target regions\n", "count_bam_variants",
+		        (int)c->reg_chr.size());
+		std::unordered_map<std::string, int32_t> tid_of;
+		for (size_t i = 0; i < rd.refs().size(); ++i) tid_of.emplace(rd.refs()[i], (int32_t)i);
+		for (size_t i = 0; i < c->reg_chr.size(); ++i) {
+			const auto it = tid_of.find(c->reg_chr[i]);
+			if (it == tid_of.end()) {
+				fprintf(stderr, "Warning: chromosome %s not found in BAM\n", c->reg_chr[i].c_str());
+				continue;
+			}
+			tid.push_back(it->second);
+			start.push_back(c->reg_start[i]);
+			end.push_back(c->reg_end[i]);
+		}
+	}
+	const bool weighted = have_index && have_regions;
+	rc = vc_bam_set_regions(c, tid.data(), start.data(), end.data(), tid.size());
+	if (rc != VC_OK) return rc;
+	if (weighted && tid.empty()) {
+		// every region is on a chromosome this file lacks: the reference fetches nothing
+		st.seconds = vc_now() - t0;
+		if (stats) *stats = st;
+		return VC_OK;
+	}
+	const size_t limit = vc_batch_bytes(BAM_BATCH_BYTES);
+	std::vector<vc_bam_rec> recs;
+	std::vector<uint8_t> data;
+	for (;;) {
+		recs.clear();
+		data.clear();
+		if (!rd.next_batch(recs, data, limit, BAM_BATCH_RECS)) break;
+		if ((rc = vc_bam_count_block(c, recs.data(), recs.size(), data.data(), data.size())) != VC_OK) break;
+		++st.blocks;
+	}
+	st.bases = rd.bases;
+	st.seqs = rd.records;
+	st.seconds = vc_now() - t0;
+	if (stats) *stats = st;
+	return rc;
+}

@@ -156,14 +156,19 @@ struct VcStager {
 		return vc_slot_wait(slot[cur]);
 	}
 	// H2D copies of the acquired slot's first n_reads reads (bytes of sequence)
-	// and launch(slot) on stream st; the slot is released by its event.
-	template <class Launch> int submit(size_t bytes, uint64_t n_reads, hipStream_t st, Launch &&launch)
+	// and launch(slot) on stream st; the slot is released by its event.  A batch
+	// that keeps its per-record data inside the byte buffer (the BAM counter's
+	// descriptors) passes per_read = false: offs and lens are not shipped.
+	template <class Launch>
+	int submit(size_t bytes, uint64_t n_reads, hipStream_t st, Launch &&launch, bool per_read = true)
 	{
 		VcSlot &s = slot[cur];
 		if (n_reads) {
 			if (bytes) HIPCK(hipMemcpyAsync(s.d_seq, s.h_seq, bytes, hipMemcpyHostToDevice, st));
-			HIPCK(hipMemcpyAsync(s.d_offs, s.h_offs, n_reads * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-			HIPCK(hipMemcpyAsync(s.d_lens, s.h_lens, n_reads * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+			if (per_read) {
+				HIPCK(hipMemcpyAsync(s.d_offs, s.h_offs, n_reads * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+				HIPCK(hipMemcpyAsync(s.d_lens, s.h_lens, n_reads * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+			}
 			const int rc = launch(s);
 			if (rc != VC_OK) return rc;
 			HIPCK(hipEventRecord(s.done, st));

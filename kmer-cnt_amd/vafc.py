@@ -54,6 +54,11 @@ EXPORTS = (
     "vc_vafset_name", "vc_vafset_snps", "vc_corr_matrix", "vc_corr_matrix_raw", "vc_corr_write", "vc_corr_tree",
     "vc_ed_create", "vc_ed_create_raw", "vc_ed_destroy", "vc_ed_count_block", "vc_ed_count_device",
     "vc_ed_finish", "vc_ed_reset", "vc_ed_set_counts", "vc_ed_set_max_ranges", "vc_ed_kernel_ms", "vc_ed_count_file",
+    "vc_bam_probe", "vc_bam_kind_name", "vc_bam_read_file", "vc_bam_read_header", "vc_bam_file_refs",
+    "vc_bam_file_ref_name", "vc_bam_file_records", "vc_bam_file_free", "vc_bam_index_usable", "vc_bam_build_regions",
+    "vc_bam_create", "vc_bam_destroy", "vc_bam_set_regions", "vc_bam_count_block", "vc_bam_count_device",
+    "vc_bam_finish", "vc_bam_reset", "vc_bam_set_counts", "vc_bam_set_long_threshold", "vc_bam_kernel_ms",
+    "vc_bam_count_file",
     "vc_synth_reads",
     "vc_debug_decode", "vc_strerror", "vc_version", "vc_build_id",
 )
@@ -222,6 +227,27 @@ def lib():
         "vc_ed_set_max_ranges": (C.c_int, [P, C.c_uint32]),
         "vc_ed_kernel_ms": (C.c_int, [P, C.POINTER(C.c_float)]),
         "vc_ed_count_file": (C.c_int, [P, C.c_char_p, C.c_int, C.POINTER(FileStats)]),
+        "vc_bam_probe": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
+        "vc_bam_kind_name": (C.c_char_p, [C.c_int]),
+        "vc_bam_read_file": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(P)]),
+        "vc_bam_read_header": (C.c_int, [C.c_char_p, C.POINTER(P)]),
+        "vc_bam_file_refs": (C.c_int, [P]),
+        "vc_bam_file_ref_name": (C.c_char_p, [P, C.c_int]),
+        "vc_bam_file_records": (C.c_uint64, [P, C.POINTER(P), C.POINTER(P), C.POINTER(C.c_uint64)]),
+        "vc_bam_file_free": (None, [P]),
+        "vc_bam_index_usable": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
+        "vc_bam_build_regions": (C.c_int, [P, P, P]),
+        "vc_bam_create": (C.c_int, [C.POINTER(P), P, C.POINTER(C.c_char_p), C.c_int, C.c_int]),
+        "vc_bam_destroy": (None, [P]),
+        "vc_bam_set_regions": (C.c_int, [P, P, P, P, C.c_size_t]),
+        "vc_bam_count_block": (C.c_int, [P, P, C.c_uint64, P, C.c_size_t]),
+        "vc_bam_count_device": (C.c_int, [P, P, C.c_uint64, P, C.c_size_t, P]),
+        "vc_bam_finish": (C.c_int, [P, P]),
+        "vc_bam_reset": (C.c_int, [P]),
+        "vc_bam_set_counts": (C.c_int, [P, P]),
+        "vc_bam_set_long_threshold": (C.c_int, [P, C.c_uint32]),
+        "vc_bam_kernel_ms": (C.c_int, [P, C.POINTER(C.c_float)]),
+        "vc_bam_count_file": (C.c_int, [P, C.c_char_p, C.c_int, C.POINTER(FileStats)]),
         "vc_synth_reads": (C.c_int, [P, P, P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64,
                                      C.c_double, P, P, C.c_uint32, P]),
         "vc_debug_decode": (C.c_int, [P, C.c_size_t, P, P, C.c_uint64, P, P]),
@@ -283,7 +309,7 @@ def check_build(paths=None) -> None:
 
 
 BINARIES = ("libvafc.so", "vaf-counter", "snp-pattern-gen", "kc-c4", "yak-count", "correlation-matrix",
-            "ed-vaf-counter")
+            "ed-vaf-counter", "bam-vaf-counter")
 
 
 def _ck(rc, what):
@@ -1385,3 +1411,177 @@ def ed_parse_args(argv):
         elif c == "e":
             opt["e"] = c_atoi(a)
     return opt, files
+
+
+# ---------------------------------------------------------------------------
+# bam-vaf-counter: ref/alt base counts at SNP positions from BAM
+# (bam-vaf-counter.c), the names of the reference's functions over vc_bam_* in
+# libvafc.so; the contract is stated in include/vafc.h
+# ---------------------------------------------------------------------------
+
+# vc_bam_rec: one record as the kernels read it
+BAM_REC = np.dtype([("tid", "<i4"), ("pos", "<i4"), ("flag", "<u4"), ("n_cigar", "<u4"), ("l_seq", "<u4"),
+                    ("reserved", "<u4"), ("off", "<u8")])
+BAM_KINDS = ("BGZF", "SAM", "CRAM", "RAW", "GZIP", "BGZF_OTHER")
+BAM_NEVER_LONG = 0xFFFFFFFF     # BamCounter.set_long_threshold: no record gets a wave
+
+
+def bam_probe(fn: str) -> str:
+    """What a file is by its first bytes (one of BAM_KINDS); FileNotFoundError."""
+    kind = C.c_int()
+    rc = lib().vc_bam_probe(fn.encode(), C.byref(kind))
+    if rc == VC_EIO:
+        raise FileNotFoundError(fn)
+    _ck(rc, "vc_bam_probe(%s)" % fn)
+    return BAM_KINDS[kind.value]
+
+
+def read_bam(fn: str, n_thread: int = 4):
+    """The host reader alone, no GPU: (reference names, records as a BAM_REC
+    array, data as uint8).  FileNotFoundError if the file cannot be opened,
+    VafcError(VC_EINVAL) if it is not BGZF BAM or its header cannot be read."""
+    h = P()
+    rc = lib().vc_bam_read_file(fn.encode(), n_thread, C.byref(h))
+    try:
+        if rc == VC_EIO:
+            raise FileNotFoundError(fn)
+        _ck(rc, "vc_bam_read_file(%s)" % fn)
+        names = [lib().vc_bam_file_ref_name(h, i).decode("latin-1") for i in range(lib().vc_bam_file_refs(h))]
+        rp, dp, nb = P(), P(), C.c_uint64()
+        n = lib().vc_bam_file_records(h, C.byref(rp), C.byref(dp), C.byref(nb))
+        recs = np.frombuffer(C.string_at(rp, n * BAM_REC.itemsize), BAM_REC).copy() if n else np.zeros(0, BAM_REC)
+        data = np.frombuffer(C.string_at(dp, nb.value), np.uint8).copy() if nb.value else np.zeros(0, np.uint8)
+        return names, recs, data
+    finally:
+        if h:
+            lib().vc_bam_file_free(h)
+
+
+def bam_header_names(fn: str):
+    """sam_hdr_read's reference names of a BGZF BAM (errors as read_bam)."""
+    h = P()
+    rc = lib().vc_bam_read_header(fn.encode(), C.byref(h))
+    try:
+        if rc == VC_EIO:
+            raise FileNotFoundError(fn)
+        _ck(rc, "vc_bam_read_header(%s)" % fn)
+        return [lib().vc_bam_file_ref_name(h, i).decode("latin-1") for i in range(lib().vc_bam_file_refs(h))]
+    finally:
+        if h:
+            lib().vc_bam_file_free(h)
+
+
+def bam_index_usable(fn: str):
+    """(usable, index file name or None): the index sam_index_load would find
+    for fn, and whether it carries a BAI or CSI magic."""
+    buf = C.create_string_buffer(4096)
+    ok = lib().vc_bam_index_usable(fn.encode(), buf, len(buf))
+    return bool(ok), (buf.value.decode() or None)
+
+
+def build_regions(db: PatternDB):
+    """build_regions (bam-vaf-counter.c:124-175): [(chr, start, end)], one
+    [pos, pos + 1) per row, sorted by chr then start, adjacent ones merged."""
+    n = db.n
+    if n <= 0:
+        return []
+    first, ends = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    m = lib().vc_bam_build_regions(db._h, _ptr(first), _ptr(ends))
+    out = []
+    for i in range(m):
+        r = db.record(int(first[i]))
+        out.append((r[0], r[1], int(ends[i])))
+    return out
+
+
+class BamCounter:
+    """Ref/alt base counts at the rows' positions over BAM records on the GPU
+    (worker_check_positions, bam-vaf-counter.c:290-318).  ref_names: the
+    reference list of the first input file, which gives every row its tid.
+    Counts are uint32[2 * n_patterns] (ref, alt interleaved)."""
+
+    def __init__(self, db: PatternDB, ref_names, device: int = 0):
+        names = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in ref_names]
+        arr = (C.c_char_p * max(1, len(names)))(*names)
+        h = P()
+        _ck(lib().vc_bam_create(C.byref(h), db._h, arr, len(names), device), "vc_bam_create")
+        self._h = h
+        self.n_counts = 2 * db.n
+        self.device = device
+
+    def set_regions(self, tid=(), start=(), end=()) -> None:
+        """The merged regions of the file counted next, tids in its own header
+        (the weights of an indexed pass); none: every record weighs 1."""
+        tid = np.ascontiguousarray(tid, dtype=np.int32)
+        start = np.ascontiguousarray(start, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        assert tid.size == start.size == end.size
+        _ck(lib().vc_bam_set_regions(self._h, _ptr(tid), _ptr(start), _ptr(end), tid.size), "vc_bam_set_regions")
+
+    def count_block(self, recs: np.ndarray, data: np.ndarray) -> None:
+        recs = np.ascontiguousarray(recs, dtype=BAM_REC)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        _ck(lib().vc_bam_count_block(self._h, _ptr(recs) if recs.size else None, recs.size,
+                                     _ptr(data) if data.size else None, data.size), "vc_bam_count_block")
+
+    def count_device(self, recs_ptr: int, n_recs: int, data_ptr: int, data_bytes: int, stream: int = 0) -> None:
+        """HBM-resident records on `stream` (as KmerMap.count_device)."""
+        _ck(lib().vc_bam_count_device(self._h, P(recs_ptr), n_recs, P(data_ptr) if data_ptr else None, data_bytes,
+                                      P(stream) if stream else None), "vc_bam_count_device")
+
+    def count_file(self, fn: str, n_thread: int = 4) -> FileStats:
+        """count_bam_variants (bam-vaf-counter.c:417-470) with its stderr lines;
+        FileNotFoundError if the file cannot be opened (the reference reports
+        it and goes on)."""
+        st = FileStats()
+        rc = lib().vc_bam_count_file(self._h, fn.encode(), n_thread, C.byref(st))
+        if rc == VC_EIO:
+            raise FileNotFoundError(fn)
+        _ck(rc, "vc_bam_count_file(%s)" % fn)
+        return st
+
+    def finish(self) -> np.ndarray:
+        counts = np.zeros(self.n_counts + 2, dtype=np.uint32)
+        _ck(lib().vc_bam_finish(self._h, _ptr(counts)), "vc_bam_finish")
+        return counts[:self.n_counts]
+
+    def reset(self) -> None:
+        _ck(lib().vc_bam_reset(self._h), "vc_bam_reset")
+
+    def set_counts(self, counts: np.ndarray) -> None:
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        assert counts.size >= self.n_counts
+        _ck(lib().vc_bam_set_counts(self._h, _ptr(counts)), "vc_bam_set_counts")
+
+    def set_long_threshold(self, ops: int) -> None:
+        """Records of more than `ops` CIGAR operations get a wave each (0:
+        every record with a CIGAR, BAM_NEVER_LONG: none); a test hook, the
+        counts do not depend on it."""
+        _ck(lib().vc_bam_set_long_threshold(self._h, ops), "vc_bam_set_long_threshold")
+
+    def kernel_ms(self) -> float:
+        ms = C.c_float()
+        _ck(lib().vc_bam_kernel_ms(self._h, C.byref(ms)), "vc_bam_kernel_ms")
+        return ms.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().vc_bam_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def create_snp_map(db: PatternDB, first_bam: str, device: int = 0) -> BamCounter:
+    """create_snp_map (bam-vaf-counter.c:187-215): the rows' tids from the
+    header of the first input file, as a counter on the device."""
+    return BamCounter(db, bam_header_names(first_bam), device)
+
+
+def count_bam_variants(fn: str, n_thread: int, snp_map: BamCounter) -> FileStats:
+    """count_bam_variants (bam-vaf-counter.c:417-470): one file into the counter."""
+    return snp_map.count_file(fn, n_thread)
