@@ -414,7 +414,11 @@ void vc_fasta_free(vc_fasta *fa);
  * (16 B each, rounded up to a power of two, at most 40 % of free HBM; 0 =
  * that maximum).
  * Replaces kc-c4's kc_c4x_t sub-tables and count_file (kc-c4.c:56-66,
- * 170-182).  vc_reset clears the table; vc_finish returns the k-mers seen. */
+ * 170-182).  vc_reset clears the table; vc_finish returns the k-mers seen.
+ * Reads may overlap, but when a call holds more reads longer than 4096 bases
+ * than seq_bytes / 4097 + 1 the surplus is not counted: vc_finish,
+ * vc_kc_histogram2 and vc_yak_bloom_select then return VC_EINVAL until
+ * vc_reset. */
 int vc_kc_create(vc_ctx **out, int k, uint64_t table_slots, int device);
 /* Count only the k-mers of partition `part` of `n_parts` (1..1024), by the
  * low 10 bits of hash64 (kc-c4.c:40-50): ((h & 1023) * n_parts) >> 10 ==

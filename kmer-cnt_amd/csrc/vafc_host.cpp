@@ -105,7 +105,7 @@ struct Kc {
 	uint64_t slots = 0;
 	uint32_t tbits = 0;
 	uint32_t n_parts = 1, part = 0;
-	unsigned long long *d_stats = nullptr;   // k-mers, distinct, overflow
+	unsigned long long *d_stats = nullptr;   // k-mers, distinct, table full, long-read list full
 	unsigned long long *d_hist = nullptr;    // up to 1024 bins + the slots counted
 	uint32_t *d_nlong = nullptr, *d_long = nullptr;
 	uint64_t *d_segstart = nullptr;
@@ -325,6 +325,7 @@ static int kc_launch(vc_ctx *c, const uint8_t *d_seq, size_t seq_bytes, const ui
                      const uint32_t *d_lens, uint64_t n_reads, hipStream_t st)
 {
 	Kc &K = *c->kc;
+	if (n_reads > 0xFFFFFFFFull) return VC_EINVAL;   // the long-read list holds u32 read indices
 	const uint64_t need = seq_bytes / (KC_LONG + 1) + 1;
 	if (need > K.long_cap) {
 		HIPCK(hipStreamSynchronize(st));
@@ -536,10 +537,13 @@ extern "C" int vc_finish(vc_ctx *c, uint32_t *counts, uint64_t *kmers)
 	HIPCK(hipStreamSynchronize(c->st));
 	c->stage.settle();
 	if (c->kc) {   // histogram mode: the k-mers seen (vc_kc_histogram gives the rest)
-		if (kmers) {
-			unsigned long long st[3];
-			HIPCK(hipMemcpy(st, c->kc->d_stats, sizeof st, hipMemcpyDeviceToHost));
-			*kmers = st[0];
+		unsigned long long st[4];
+		HIPCK(hipMemcpy(st, c->kc->d_stats, sizeof st, hipMemcpyDeviceToHost));
+		if (kmers) *kmers = st[0];
+		if (st[3]) {
+			fprintf(stderr, "[E::vafc] more reads longer than %d bases than the long-read list holds "
+			        "(overlapping reads?): counts incomplete\n", KC_LONG);
+			return VC_EINVAL;
 		}
 		return VC_OK;
 	}
@@ -561,7 +565,7 @@ extern "C" int vc_reset(vc_ctx *c)
 	if (c->kc) {
 		Kc &K = *c->kc;
 		HIPCK(hipMemsetAsync(K.d_table, 0, K.slots * 16, c->st));
-		HIPCK(hipMemsetAsync(K.d_stats, 0, 3 * sizeof(unsigned long long), c->st));
+		HIPCK(hipMemsetAsync(K.d_stats, 0, 4 * sizeof(unsigned long long), c->st));
 		if (K.track_first) HIPCK(hipMemsetAsync(K.d_first, 0xFF, K.slots * 8, c->st));
 		K.read_base = 0;
 		K.lookup_only = false;
@@ -1458,7 +1462,7 @@ extern "C" int vc_kc_create(vc_ctx **out, int k, uint64_t table_slots, int devic
 	}
 	K->tbits = tbits;
 	K->slots = (uint64_t)1 << tbits;
-	if (hipMalloc(&K->d_table, K->slots * 16) != hipSuccess || hipMalloc(&K->d_stats, 3 * 8) != hipSuccess ||
+	if (hipMalloc(&K->d_table, K->slots * 16) != hipSuccess || hipMalloc(&K->d_stats, 4 * 8) != hipSuccess ||
 	    hipMalloc(&K->d_hist, 1025 * 8) != hipSuccess || hipMalloc(&K->d_nlong, 4) != hipSuccess) {
 		vc_destroy(c);
 		return VC_EHIP;
@@ -1510,10 +1514,11 @@ extern "C" int vc_kc_histogram2(vc_ctx *c, uint64_t *hist, uint32_t n_bins, uint
 	Kc &K = *c->kc;
 	HIPCK(hipSetDevice(c->dev));
 	HIPCK(hipStreamSynchronize(c->st));
-	unsigned long long st[3];
+	unsigned long long st[4];
 	HIPCK(hipMemcpy(st, K.d_stats, sizeof st, hipMemcpyDeviceToHost));
 	if (kmers) *kmers = st[0];
 	if (distinct) *distinct = st[1];
+	if (st[3]) return VC_EINVAL;   // long reads were left out (vc_finish said so): no histogram of the rest
 	if (st[2] || st[1] > K.slots / 100 * 85) return VC_EFULL;
 	uint64_t counted = 0;
 	int rc = kc_hist(c, hist, n_bins, min_count, &counted);
@@ -1546,8 +1551,9 @@ extern "C" int vc_yak_bloom_select(vc_ctx *c, int pre, int bf_shift, int n_hash)
 	Kc &K = *c->kc;
 	HIPCK(hipSetDevice(c->dev));
 	HIPCK(hipStreamSynchronize(c->st));
-	unsigned long long st[3];
+	unsigned long long st[4];
 	HIPCK(hipMemcpy(st, K.d_stats, sizeof st, hipMemcpyDeviceToHost));
+	if (st[3]) return VC_EINVAL;   // long reads were left out (vc_finish said so)
 	if (st[2] || st[1] > K.slots / 100 * 85) return VC_EFULL;
 	// yak_ch_init / yak_bf_init (yak-count.c:71-80, 115-121): filters exist only
 	// for n_hash > 0 and 9 <= bf_shift - pre <= 55

@@ -26,7 +26,7 @@ struct KcArgs {
 	int lookup_only;             // yak pass 2: count only keys already present and not dropped
 	int k;
 	uint64_t kmask;
-	unsigned long long *stats;   // [0] k-mers seen, [1] distinct inserted, [2] overflow
+	unsigned long long *stats;   // [0] k-mers seen, [1] distinct inserted, [2] table full, [3] long list full
 	uint32_t *nlong;
 	uint32_t *longlist;
 	uint32_t long_cap;

@@ -154,6 +154,8 @@ __global__ __launch_bounds__(KC_THREADS) void kc_count_kernel(KcArgs A)
 		if (len > KC_LONG) {
 			const uint32_t slot = atomicAdd(A.nlong, 1u);
 			if (slot < A.long_cap) A.longlist[slot] = (uint32_t)r;
+			else   // more long reads than seq_bytes / (KC_LONG + 1) + 1: the reads overlap
+				__hip_atomic_store(&A.stats[3], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 			continue;
 		}
 		if (!L.overflow && __hip_atomic_load(&A.stats[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
