@@ -713,6 +713,178 @@ int vc_bam_kernel_ms(vc_bam *b, float *ms);
 int vc_bam_count_file(vc_bam *b, const char *path, int n_threads, vc_file_stats *st);
 
 /* ------------------------------------------------------------------ */
+/* vcf-vaf-counter: genotypes of a VCF as .vaf counts                  */
+/* (vcf-vaf-counter.c; line rules of htslib's vcf.c vcf_parse)         */
+/* ------------------------------------------------------------------ */
+
+/* The contract, read from vcf-vaf-counter.c and htslib's vcf.c and pinned by
+ * the goldens of tests/golden/vcf:
+ *
+ * 1. Patterns load as vc_patterns_load (the fscanf of vcf-vaf-counter.c:52
+ *    is vaf-counter.c:164's); the .vaf writer is vc_write_vaf (:246-273).
+ * 2. Row matching (find_pattern :83-92, called at :126).  A record's row is
+ *    the FIRST row in file order with strcmp(chr, CHROM) == 0 and start ==
+ *    (int)(POS - 1): the cast truncates a 64-bit position (POS = 2^32 + 100 is
+ *    start 99), POS 0 and an empty POS are start -1.  A later row with the
+ *    same chr and start never receives anything.  POS may have leading zeros
+ *    or a '+' (hts_str2uint).  A CHROM the header does not declare is matched
+ *    like any other (vcf.c:3686-3696 only warns).
+ * 3. Allele filter (:130-135): exactly two alleles (ALT "." is one, "T,G" is
+ *    three), REF one byte and ALT one byte, both equal to that first row's
+ *    ref and alt exactly (lower case does not match).  A mismatch does not
+ *    fall through to a duplicate row.
+ * 4. GT (:138-148).  ngt = samples * the largest ploidy on the line; the
+ *    reference reads flat entries 2s and 2s+1 for sample index s whatever the
+ *    ploidy, and skips the record if 2s+1 >= ngt.  A missing allele ('.'), a
+ *    missing trailing GT field and a padding entry all give an allele below
+ *    0: skipped.  '/' and '|' are the same.  GT must be Type=String in the
+ *    header or absent from it; with another type bcf_get_genotypes refuses.
+ * 5. AD (:155-165) is used only if the header declares it Type=Integer (an
+ *    undeclared tag is taken as String, vcf.c:2856-2880).  nad = samples *
+ *    the longest AD vector on the line; flat entries 2s and 2s+1 are read if
+ *    2s+1 < nad, and if both differ from the missing code ('.'), ref =
+ *    first, alt = second, depth = their sum.  A padding entry is not missing:
+ *    it enters as the vector-end value 0x80000001.
+ * 6. DP (:168-188) is tried if depth is still 0 (AD 0,0 included), must be
+ *    Type=Integer; flat entry s must exist and not be missing.  Genotype 0/0
+ *    gives (DP, 0), 1/1 gives (0, DP), anything else (DP/2, DP - DP/2).
+ * 7. depth < min_depth: skipped.  Otherwise the row's two counts are SET,
+ *    not added: the last qualifying record in file order wins, and with
+ *    min_depth <= 0 a record of depth 0 sets 0 0 (:191-195).
+ * 8. What ends the file, keeping everything before it, exit code 0: a line
+ *    vcf_parse rejects (:118).  Fewer than 8 columns; a POS that is not
+ *    [+]digits below 2^62; a FORMAT tag "."; more than 255 tags; a tag
+ *    declared Type=Flag; a sample column with more fields than FORMAT; fewer
+ *    sample columns than the header has samples (more are ignored); a GT value
+ *    that is neither a number nor '.'; a character other than ':' behind a
+ *    value (vcf.c:3216-3229).  An empty line and a '#' line behind the header
+ *    are such lines.  These are not: an empty CHROM (a contig like any other,
+ *    :3686-3696); an empty FORMAT tag (an undeclared tag like any other,
+ *    :2863-2880); a FORMAT column with no sample column behind it
+ *    (:3349-3350 turn the error into success: the line is skipped).  One line
+ *    ends the PROGRAM: GT named in FORMAT and present in no sample column, on a
+ *    line that passes items 2 and 3, makes bcf_get_format_values call exit(1);
+ *    no .vaf is written.  An input that cannot be opened, or whose header
+ *    cannot be read (it does not begin with ##fileformat=VCF, a data line comes
+ *    before the #CHROM line, there is no #CHROM line) gets the reference's
+ *    Error: line and counts nothing; the all-zero .vaf is still written, exit 0.
+ * 9. Input: plain text, gzip and BGZF (read as the multi-member gzip it is);
+ *    a '\r' in front of the '\n' is dropped; a last line needs no '\n'.
+ * 10. Deviations.  BCF is refused with a message naming the format.  htslib's
+ *    own [W::/[E:: lines are not reproduced.  A negative sample index counts
+ *    nothing.  Item 8 is reproduced where the first five columns of ANY line
+ *    are malformed, and for every defect named there of a line that passes
+ *    items 2 and 3; a line that does not pass them is never looked at behind
+ *    its ALT column, where the reference might stop.  FILTER and INFO are not
+ *    validated.  Header lines are read for their FORMAT IDs and types only
+ *    (first declaration wins).  Compressed input that is damaged or cut off
+ *    ends as if the text ended there (htslib stops with a read error in front
+ *    of the cut line).  AD/DP values outside int32 and sums that overflow int
+ *    are outside the contract. */
+
+typedef struct vc_vcf vc_vcf;
+typedef struct vc_vcf_header vc_vcf_header;
+
+/* Bytes of text one workgroup scans per step (256 lanes x 16 bytes): a line
+ * belongs to the tile its first byte is in. */
+#define VC_VCF_TILE_BYTES 4096
+
+/* One reported line: the file offset of its first byte and the first row
+ * with its (CHROM, POS - 1) whose ref / alt equal its REF / ALT, or row = -1
+ * for a line the device leaves to the host (fewer than five tabs or a control
+ * character in the first five columns, an empty CHROM or one longer than 255
+ * bytes (neither is malformed: the host then matches the line itself), a POS
+ * that is not 1..18 digits). */
+typedef struct {
+	uint64_t off;
+	int32_t row;
+	uint32_t reserved;   /* 0 */
+} vc_vcf_hit;
+
+/* Kinds of input, vc_vcf_probe: VC_VCF_BCF* are refused, VC_VCF_OTHER is not
+ * VCF (the header read fails as in the reference). */
+enum { VC_VCF_PLAIN = 0, VC_VCF_GZIP = 1, VC_VCF_BGZF = 2, VC_VCF_BCF = 3, VC_VCF_OTHER = 4 };
+/* What a file is by its first bytes (a compressed one by its first inflated
+ * bytes); VC_EIO if it cannot be opened. */
+int vc_vcf_probe(const char *path, int *kind);
+const char *vc_vcf_kind_name(int kind);
+
+/* Host only.  The header of VCF text: *out holds the sample count and the
+ * declared FORMAT types, *body_off the offset of the first data line.
+ * Returns VC_OK, VC_EINVAL (item 8: no header), or VC_VCF_MORE when text ends
+ * before the #CHROM line does and final == 0. */
+#define VC_VCF_MORE 1
+/* vc_vcf_count_file: a line ended the program (item 8); the counts are void. */
+#define VC_VCF_ABORTED 2
+int vc_vcf_header_parse(const uint8_t *text, size_t len, int final, vc_vcf_header **out, size_t *body_off);
+int vc_vcf_header_samples(const vc_vcf_header *h);
+/* Declared type of a FORMAT tag: htslib's BCF_HT_* (0 Flag, 1 Integer, 2
+ * Float, 3 String or Character), -1 undeclared. */
+int vc_vcf_header_type(const vc_vcf_header *h, const char *tag);
+void vc_vcf_header_free(vc_vcf_header *h);
+
+enum { VC_VCF_SKIP = 0, VC_VCF_SET = 1, VC_VCF_END = 2, VC_VCF_ABORT = 3 };
+typedef struct {
+	int32_t verdict;       /* VC_VCF_*: what the line does to a row it hits (items 4-8; ABORT: the program ends) */
+	int32_t head_ok;       /* its first five columns are well-formed (0: verdict is VC_VCF_END) */
+	int64_t pos;           /* POS - 1, untruncated */
+	uint32_t chrom_len;    /* CHROM is line[0 .. chrom_len) */
+	int32_t n_allele;
+	uint32_t ref_len, alt_len;   /* bytes of REF and of the first ALT allele */
+	uint8_t ref, alt;      /* their first bytes */
+	uint8_t reserved[2];
+	uint32_t ref_count, alt_count;   /* verdict VC_VCF_SET */
+} vc_vcf_verdict;
+/* Host only.  One line (with or without its "\n" / "\r\n") under items 4-8 for
+ * sample index sample_idx. */
+int vc_vcf_eval_line(const vc_vcf_header *h, const uint8_t *line, size_t len, int sample_idx, int min_depth,
+                     vc_vcf_verdict *out);
+
+/* The panel of db as a hash table on HIP device `device`: keyed by (hash of
+ * chr, start), one entry per distinct (chr, start) holding the first such
+ * row, the chr bytes beside it. */
+int vc_vcf_create(vc_vcf **out, const vc_patterns *db, int device);
+/* The same from arrays, with table_slots entries (a power of two >= the
+ * number of distinct (chr, start), 0: chosen as vc_vcf_create does), so that a
+ * test can force every probe to chain.  Names are at most 255 bytes. */
+int vc_vcf_create_raw(vc_vcf **out, const char *const *chr, const int32_t *start, const char *ref, const char *alt,
+                      size_t n, size_t table_slots, int device);
+void vc_vcf_destroy(vc_vcf *v);
+/* Scan a block of host text that begins at a line start (staged through
+ * pinned memory, asynchronous, text reusable on return).  file_off is the
+ * offset of text[0], added to every reported offset.  final == 0: the bytes
+ * behind the block's last '\n' are left to the next block; *consumed is the
+ * number of bytes scanned (0 when the block holds no '\n').  Lines found are
+ * added to those vc_vcf_hits returns. */
+int vc_vcf_scan_block(vc_vcf *v, const uint8_t *text, size_t len, uint64_t file_off, int final, size_t *consumed);
+/* The same for HBM-resident text (any alignment) on `stream`, with
+ * vc_count_device's ordering contract; the bytes consumed come with
+ * vc_vcf_hits.  d_text must stay valid until then; a scan still pending from
+ * an earlier call is collected (synchronised) first. */
+int vc_vcf_scan_device(vc_vcf *v, const uint8_t *d_text, size_t len, uint64_t file_off, int final, void *stream);
+/* Wait for the scans since the last call; their lines sorted by offset
+ * (valid until the next call on v) and the bytes the last scan consumed.  A
+ * scan that found more lines than the list holds is run again with a larger
+ * list: the result does not depend on the capacity. */
+int vc_vcf_hits(vc_vcf *v, const vc_vcf_hit **hits, size_t *n_hits, size_t *consumed);
+/* Test hooks: capacity of the device's hit list (default 1 << 20), and the
+ * bytes of one block of vc_vcf_count_file (default 32 MiB; a longer line
+ * grows the block). */
+int vc_vcf_set_max_hits(vc_vcf *v, size_t max_hits);
+int vc_vcf_set_block_bytes(vc_vcf *v, size_t bytes);
+/* Elapsed milliseconds of the kernels of the last scan. */
+int vc_vcf_kernel_ms(vc_vcf *v, float *ms);
+/* process_vcf (vcf-vaf-counter.c:95-204) with its stderr lines: the header on
+ * the host, the body through the kernel block by block, the lines it reports
+ * through vc_vcf_eval_line in file order; counts[2 * n_patterns] receives
+ * item 7's assignments (it is not zeroed).  n_threads inflate gzip input.
+ * VC_EIO: cannot be opened; VC_EINVAL: no VCF header, or BCF (nothing is
+ * counted in either case); VC_VCF_ABORTED: item 8's line that ends the program.  st: seqs = lines reported by the device, bases =
+ * bytes of text, blocks = blocks scanned. */
+int vc_vcf_count_file(vc_vcf *v, const char *path, int sample_idx, int min_depth, int n_threads, uint32_t *counts,
+                      vc_file_stats *st);
+
+/* ------------------------------------------------------------------ */
 /* Synthetic workload (bench / tests): the generator of vafc_synth.py,  */
 /* evaluated on the device.                                            */
 /* ------------------------------------------------------------------ */

@@ -59,6 +59,10 @@ EXPORTS = (
     "vc_bam_create", "vc_bam_destroy", "vc_bam_set_regions", "vc_bam_count_block", "vc_bam_count_device",
     "vc_bam_finish", "vc_bam_reset", "vc_bam_set_counts", "vc_bam_set_long_threshold", "vc_bam_kernel_ms",
     "vc_bam_count_file",
+    "vc_vcf_probe", "vc_vcf_kind_name", "vc_vcf_header_parse", "vc_vcf_header_samples", "vc_vcf_header_type",
+    "vc_vcf_header_free", "vc_vcf_eval_line", "vc_vcf_create", "vc_vcf_create_raw", "vc_vcf_destroy",
+    "vc_vcf_scan_block", "vc_vcf_scan_device", "vc_vcf_hits", "vc_vcf_set_max_hits", "vc_vcf_set_block_bytes",
+    "vc_vcf_kernel_ms", "vc_vcf_count_file",
     "vc_synth_reads",
     "vc_debug_decode", "vc_strerror", "vc_version", "vc_build_id",
 )
@@ -98,6 +102,13 @@ class GzShareCrc(C.Structure):
 
     def as_dict(self):
         return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+class VcfVerdict(C.Structure):
+    """vc_vcf_verdict: one VCF line under items 4-8 of the vcf-vaf-counter contract."""
+    _fields_ = [("verdict", C.c_int32), ("head_ok", C.c_int32), ("pos", C.c_int64), ("chrom_len", C.c_uint32),
+                ("n_allele", C.c_int32), ("ref_len", C.c_uint32), ("alt_len", C.c_uint32), ("ref", C.c_uint8),
+                ("alt", C.c_uint8), ("reserved", C.c_uint8 * 2), ("ref_count", C.c_uint32), ("alt_count", C.c_uint32)]
 
 
 NO_OFFSET = (1 << 64) - 1   # vc_range_info's UINT64_MAX
@@ -248,6 +259,23 @@ def lib():
         "vc_bam_set_long_threshold": (C.c_int, [P, C.c_uint32]),
         "vc_bam_kernel_ms": (C.c_int, [P, C.POINTER(C.c_float)]),
         "vc_bam_count_file": (C.c_int, [P, C.c_char_p, C.c_int, C.POINTER(FileStats)]),
+        "vc_vcf_probe": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
+        "vc_vcf_kind_name": (C.c_char_p, [C.c_int]),
+        "vc_vcf_header_parse": (C.c_int, [P, C.c_size_t, C.c_int, C.POINTER(P), C.POINTER(C.c_size_t)]),
+        "vc_vcf_header_samples": (C.c_int, [P]),
+        "vc_vcf_header_type": (C.c_int, [P, C.c_char_p]),
+        "vc_vcf_header_free": (None, [P]),
+        "vc_vcf_eval_line": (C.c_int, [P, P, C.c_size_t, C.c_int, C.c_int, C.POINTER(VcfVerdict)]),
+        "vc_vcf_create": (C.c_int, [C.POINTER(P), P, C.c_int]),
+        "vc_vcf_create_raw": (C.c_int, [C.POINTER(P), C.POINTER(C.c_char_p), P, P, P, C.c_size_t, C.c_size_t, C.c_int]),
+        "vc_vcf_destroy": (None, [P]),
+        "vc_vcf_scan_block": (C.c_int, [P, P, C.c_size_t, C.c_uint64, C.c_int, C.POINTER(C.c_size_t)]),
+        "vc_vcf_scan_device": (C.c_int, [P, P, C.c_size_t, C.c_uint64, C.c_int, P]),
+        "vc_vcf_hits": (C.c_int, [P, C.POINTER(P), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+        "vc_vcf_set_max_hits": (C.c_int, [P, C.c_size_t]),
+        "vc_vcf_set_block_bytes": (C.c_int, [P, C.c_size_t]),
+        "vc_vcf_kernel_ms": (C.c_int, [P, C.POINTER(C.c_float)]),
+        "vc_vcf_count_file": (C.c_int, [P, C.c_char_p, C.c_int, C.c_int, C.c_int, P, C.POINTER(FileStats)]),
         "vc_synth_reads": (C.c_int, [P, P, P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64,
                                      C.c_double, P, P, C.c_uint32, P]),
         "vc_debug_decode": (C.c_int, [P, C.c_size_t, P, P, C.c_uint64, P, P]),
@@ -309,7 +337,7 @@ def check_build(paths=None) -> None:
 
 
 BINARIES = ("libvafc.so", "vaf-counter", "snp-pattern-gen", "kc-c4", "yak-count", "correlation-matrix",
-            "ed-vaf-counter", "bam-vaf-counter")
+            "ed-vaf-counter", "bam-vaf-counter", "vcf-vaf-counter")
 
 
 def _ck(rc, what):
@@ -1585,3 +1613,183 @@ def create_snp_map(db: PatternDB, first_bam: str, device: int = 0) -> BamCounter
 def count_bam_variants(fn: str, n_thread: int, snp_map: BamCounter) -> FileStats:
     """count_bam_variants (bam-vaf-counter.c:417-470): one file into the counter."""
     return snp_map.count_file(fn, n_thread)
+
+
+# --------------------------------------------------------------------------
+# vcf-vaf-counter: genotypes of a VCF as .vaf counts (vcf-vaf-counter.c), the
+# names of the reference's functions over vc_vcf_* in include/vafc.h
+# --------------------------------------------------------------------------
+
+# vc_vcf_hit: one line the device reports (row -1: left to the host)
+VCF_HIT = np.dtype([("off", "<u8"), ("row", "<i4"), ("reserved", "<u4")])
+VCF_TILE_BYTES = 4096          # VC_VCF_TILE_BYTES
+VCF_SKIP, VCF_SET, VCF_END, VCF_ABORT = 0, 1, 2, 3
+VCF_ABORTED = 2                # VC_VCF_ABORTED
+VCF_MORE = 1                   # VC_VCF_MORE
+VCF_KINDS = ("plain", "gzip", "bgzf", "bcf", "other")
+
+
+def vcf_probe(fn: str) -> str:
+    """What a file is by its first bytes: one of VCF_KINDS; FileNotFoundError."""
+    kind = C.c_int()
+    rc = lib().vc_vcf_probe(fn.encode(), C.byref(kind))
+    if rc == VC_EIO:
+        raise FileNotFoundError(fn)
+    _ck(rc, "vc_vcf_probe(%s)" % fn)
+    return VCF_KINDS[kind.value]
+
+
+class VcfHeader:
+    """Sample count and declared FORMAT types of VCF text (host only).
+    body: the offset of the first data line."""
+
+    def __init__(self, text: bytes, final: bool = True):
+        h, body = P(), C.c_size_t()
+        buf = C.create_string_buffer(bytes(text), len(text))
+        rc = lib().vc_vcf_header_parse(C.cast(buf, P), len(text), int(final), C.byref(h), C.byref(body))
+        if rc == VCF_MORE:
+            raise EOFError("the #CHROM line is not complete")
+        _ck(rc, "vc_vcf_header_parse")
+        self._h = h
+        self.body = body.value
+
+    @property
+    def n_samples(self) -> int:
+        return lib().vc_vcf_header_samples(self._h)
+
+    def type_of(self, tag: str) -> int:
+        """htslib's BCF_HT_* of a FORMAT tag (0 Flag, 1 Integer, 2 Float, 3 String), -1 undeclared."""
+        return lib().vc_vcf_header_type(self._h, tag.encode())
+
+    def eval_line(self, line: bytes, sample_idx: int = 0, min_depth: int = 1) -> VcfVerdict:
+        """One data line under items 4-8 (vc_vcf_eval_line)."""
+        v = VcfVerdict()
+        buf = C.create_string_buffer(bytes(line), len(line))
+        _ck(lib().vc_vcf_eval_line(self._h, C.cast(buf, P), len(line), sample_idx, min_depth, C.byref(v)),
+            "vc_vcf_eval_line")
+        return v
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().vc_vcf_header_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class VcfMatcher:
+    """The panel as a hash table on the GPU and the kernel that joins raw VCF
+    text against it (find_pattern, vcf-vaf-counter.c:83-92, for every line at
+    once).  Built from a PatternDB, or from rows [(chr, start, ref, alt)] with a
+    forced table size (table_slots, a power of two)."""
+
+    def __init__(self, db: PatternDB = None, rows=None, table_slots: int = 0, device: int = 0):
+        h = P()
+        if db is not None:
+            _ck(lib().vc_vcf_create(C.byref(h), db._h, device), "vc_vcf_create")
+            self.n_rows = db.n
+        else:
+            rows = list(rows)
+            b = [bytes(x) if not isinstance(x, str) else x.encode("latin-1") for x in (r[0] for r in rows)]
+            names = (C.c_char_p * max(1, len(rows)))(*b)
+            start = np.ascontiguousarray([r[1] for r in rows], dtype=np.int32)
+            ref = np.frombuffer(b"".join(bytes(r[2][:1]) if not isinstance(r[2], str) else r[2].encode() for r in rows),
+                                dtype=np.uint8).copy()
+            alt = np.frombuffer(b"".join(bytes(r[3][:1]) if not isinstance(r[3], str) else r[3].encode() for r in rows),
+                                dtype=np.uint8).copy()
+            _ck(lib().vc_vcf_create_raw(C.byref(h), names, _ptr(start) if rows else None, _ptr(ref) if rows else None,
+                                        _ptr(alt) if rows else None, len(rows), table_slots, device), "vc_vcf_create_raw")
+            self.n_rows = len(rows)
+        self._h = h
+        self.device = device
+
+    def scan_block(self, text: bytes, file_off: int = 0, final: bool = True) -> int:
+        """Scan host text that begins at a line start; returns the bytes consumed."""
+        consumed = C.c_size_t()
+        buf = C.create_string_buffer(bytes(text), len(text))
+        _ck(lib().vc_vcf_scan_block(self._h, C.cast(buf, P), len(text), file_off, int(final), C.byref(consumed)),
+            "vc_vcf_scan_block")
+        return consumed.value
+
+    def scan_device(self, text_ptr: int, n_bytes: int, file_off: int = 0, final: bool = True, stream: int = 0) -> None:
+        """HBM-resident text (any alignment) on `stream` (as KmerMap.count_device)."""
+        _ck(lib().vc_vcf_scan_device(self._h, P(text_ptr), n_bytes, file_off, int(final), P(stream) if stream else None),
+            "vc_vcf_scan_device")
+
+    def hits(self):
+        """(the lines reported since the last call as a VCF_HIT array sorted by
+        offset, the bytes the last scan consumed)."""
+        hp, n, consumed = P(), C.c_size_t(), C.c_size_t()
+        _ck(lib().vc_vcf_hits(self._h, C.byref(hp), C.byref(n), C.byref(consumed)), "vc_vcf_hits")
+        if n.value == 0:
+            return np.zeros(0, VCF_HIT), consumed.value
+        raw = C.string_at(hp, n.value * VCF_HIT.itemsize)
+        return np.frombuffer(raw, dtype=VCF_HIT).copy(), consumed.value
+
+    def set_max_hits(self, n: int) -> None:
+        _ck(lib().vc_vcf_set_max_hits(self._h, n), "vc_vcf_set_max_hits")
+
+    def set_block_bytes(self, n: int) -> None:
+        _ck(lib().vc_vcf_set_block_bytes(self._h, n), "vc_vcf_set_block_bytes")
+
+    def kernel_ms(self) -> float:
+        ms = C.c_float()
+        _ck(lib().vc_vcf_kernel_ms(self._h, C.byref(ms)), "vc_vcf_kernel_ms")
+        return ms.value
+
+    def count_file(self, fn: str, sample_idx: int = 0, min_depth: int = 1, n_thread: int = 4, counts=None):
+        """process_vcf with its stderr lines: (counts uint32[2 * n_rows], FileStats).
+        FileNotFoundError if the file cannot be opened, VafcError(VC_EINVAL) if
+        it has no VCF header or is BCF (the reference reports both and goes on),
+        VafcError(VCF_ABORTED) at the line that ends the reference's process."""
+        if counts is None:
+            counts = np.zeros(2 * self.n_rows + 2, dtype=np.uint32)
+        st = FileStats()
+        rc = lib().vc_vcf_count_file(self._h, fn.encode(), sample_idx, min_depth, n_thread, _ptr(counts), C.byref(st))
+        if rc == VC_EIO:
+            raise FileNotFoundError(fn)
+        _ck(rc, "vc_vcf_count_file(%s)" % fn)
+        return counts[:2 * self.n_rows], st
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().vc_vcf_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def find_pattern(db: PatternDB, chr_: str, pos: int) -> int:
+    """find_pattern (vcf-vaf-counter.c:83-92): the first row with this chr and
+    start, or -1 (the host's scan; the device answers the same from its table)."""
+    for i in range(db.n):
+        c, start = db.record(i)[:2]
+        if c == chr_ and start == pos:
+            return i
+    return -1
+
+
+def process_vcf(fn: str, db: PatternDB, sample_idx: int = 0, min_depth: int = 1, device: int = 0) -> np.ndarray:
+    """process_vcf (vcf-vaf-counter.c:95-204): the counts a VCF sets, uint32[2 *
+    n_patterns]; a file that cannot be opened or has no header is reported on
+    stderr and sets nothing, as in the reference."""
+    m = VcfMatcher(db, device=device)
+    try:
+        try:
+            return m.count_file(fn, sample_idx, min_depth)[0]
+        except FileNotFoundError:
+            return np.zeros(2 * db.n, dtype=np.uint32)
+        except VafcError as e:
+            if e.code != VC_EINVAL:
+                raise
+            return np.zeros(2 * db.n, dtype=np.uint32)
+    finally:
+        m.close()
