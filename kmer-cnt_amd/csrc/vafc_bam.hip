@@ -238,24 +238,15 @@ const size_t BAM_BATCH_RECS = (size_t)1 << 19;
 
 } // namespace
 
-struct vc_bam {
-	int dev = 0;
-	int n_cu = 256;
+struct vc_bam : VcDevice {
 	uint32_t n_pat = 0, n_rows = 0;
-	hipStream_t st = nullptr;
-	uint64_t *d_row_key = nullptr;
-	uint2 *d_row_info = nullptr;
-	uint32_t *d_counts = nullptr, *d_flags = nullptr;
-	uint64_t *d_reg_s = nullptr, *d_reg_e = nullptr;
+	VcDevBuf<uint64_t> d_row_key;
+	VcDevBuf<uint2> d_row_info;
+	VcDevBuf<uint32_t> d_counts, d_flags;   // 2 * n_pat + 2, 1
+	VcDevBuf<uint64_t> d_reg_s, d_reg_e;    // one capacity (vc_bam_set_regions)
 	uint32_t n_reg = 0;
-	size_t reg_cap = 0;
-	uint32_t *d_long_list = nullptr, *d_long_n = nullptr;
-	uint64_t long_cap = 0;
+	VcDevBuf<uint32_t> d_long_list, d_long_n;
 	uint32_t long_thr = 64;
-	VcStager stage;
-	VcStreamBridge bridge;
-	hipEvent_t t0 = nullptr, t1 = nullptr;
-	bool timed = false;
 	// the rows as build_regions sees them: merged regions by chromosome name
 	std::vector<std::string> reg_chr;
 	std::vector<int32_t> reg_start, reg_end;
@@ -267,14 +258,7 @@ int launch(vc_bam *c, const vc_bam_rec *d_recs, uint64_t n_recs, const uint8_t *
 {
 	if (n_recs == 0) return VC_OK;
 	if (n_recs > 0xFFFFFFFFull || ((uintptr_t)d_recs & 7) || ((uintptr_t)d_data & 3)) return VC_EINVAL;
-	if (n_recs > c->long_cap) {   // hipFree waits for the kernels that still use the old list
-		if (c->d_long_list) HIPCK(hipFree(c->d_long_list));
-		c->d_long_list = nullptr;
-		c->long_cap = 0;
-		const uint64_t cap = n_recs + n_recs / 4 + 1024;
-		HIPCK(hipMalloc((void **)&c->d_long_list, cap * sizeof(uint32_t)));
-		c->long_cap = cap;
-	}
+	if (n_recs > c->d_long_list.cap) HIPCK(c->d_long_list.grow(n_recs + n_recs / 4 + 1024));
 	VcBamArgs A;
 	A.recs = d_recs;
 	A.n_recs = n_recs;
@@ -291,8 +275,8 @@ int launch(vc_bam *c, const vc_bam_rec *d_recs, uint64_t n_recs, const uint8_t *
 	A.long_n = c->d_long_n;
 	A.counts = c->d_counts;
 	A.flags = c->d_flags;
-	HIPCK(hipMemsetAsync(c->d_long_n, 0, sizeof(uint32_t), st));
-	HIPCK(hipEventRecord(c->t0, st));
+	HIPCK(c->d_long_n.zero_async(st));
+	HIPCK(c->timer.begin(st));
 	const unsigned grid = (unsigned)((n_recs + BAM_BLOCK - 1) / BAM_BLOCK);
 	hipLaunchKernelGGL(bam_short_kernel, dim3(grid), dim3(BAM_BLOCK), 0, st, A);
 	HIPCK(hipGetLastError());
@@ -301,31 +285,14 @@ int launch(vc_bam *c, const vc_bam_rec *d_recs, uint64_t n_recs, const uint8_t *
 	if (lgrid > (n_recs + 3) / 4) lgrid = (n_recs + 3) / 4;
 	hipLaunchKernelGGL(bam_long_kernel, dim3((unsigned)lgrid), dim3(BAM_BLOCK), 0, st, A);
 	HIPCK(hipGetLastError());
-	HIPCK(hipEventRecord(c->t1, st));
-	c->timed = true;
+	HIPCK(c->timer.end(st));
 	return VC_OK;
 }
 
-} // namespace
-
-extern "C" int vc_bam_create(vc_bam **out, const vc_patterns *db, const char *const *ref_names, int n_refs, int device)
+// The rows and regions of an open handle, on the host and on the device.
+int bam_fill(vc_bam *c, const vc_patterns *db, const char *const *ref_names, int n_refs)
 {
-	if (!out || !db || n_refs < 0 || (n_refs && !ref_names)) return VC_EINVAL;
-	*out = nullptr;
-	const int n = vc_patterns_count(db);
-	if (n > (0x7FFFFFFF >> 1)) return VC_ETOOMANY;
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VC_ENODEV;
-	if (device < 0 || device >= ndev) return VC_EINVAL;
-	HIPCK(hipSetDevice(device));
-	vc_bam *c = new (std::nothrow) vc_bam;
-	if (!c) return VC_ENOMEM;
-	c->dev = device;
-	c->n_pat = (uint32_t)n;
-	hipDeviceProp_t prop;
-	if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-		c->n_cu = prop.multiProcessorCount;
-
+	const int n = (int)c->n_pat;
 	// create_snp_map (bam-vaf-counter.c:187-215): tids and the two warnings, in row order
 	std::unordered_map<std::string, int32_t> tid_of;
 	for (int i = 0; i < n_refs; ++i) tid_of.emplace(ref_names[i], i);
@@ -339,10 +306,7 @@ extern "C" int vc_bam_create(vc_bam **out, const vc_patterns *db, const char *co
 		const char *chr = nullptr;
 		int start = 0;
 		char ref = 0, alt = 0;
-		if (vc_pattern_fields(db, i, &chr, &start, nullptr, &ref, &alt, nullptr, nullptr) != VC_OK) {
-			delete c;
-			return VC_EINVAL;
-		}
+		if (vc_pattern_fields(db, i, &chr, &start, nullptr, &ref, &alt, nullptr, nullptr) != VC_OK) return VC_EINVAL;
 		const auto it = tid_of.find(chr);
 		if (it == tid_of.end()) {
 			fprintf(stderr, "Warning: chromosome %s not found in BAM header\n", chr);
@@ -379,33 +343,33 @@ extern "C" int vc_bam_create(vc_bam **out, const vc_patterns *db, const char *co
 		}
 	}
 
-#define TRY(call)                                                                                  \
-	do {                                                                                           \
-		hipError_t e_ = (call);                                                                    \
-		if (e_ != hipSuccess) {                                                                    \
-			fprintf(stderr, "[E::vafc] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_),     \
-			        __FILE__, __LINE__);                                                           \
-			vc_bam_destroy(c);                                                                     \
-			return VC_EHIP;                                                                        \
-		}                                                                                          \
-	} while (0)
-	TRY(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
-	TRY(hipMalloc((void **)&c->d_row_key, keys.size() * sizeof(uint64_t)));
-	TRY(hipMemcpy(c->d_row_key, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-	TRY(hipMalloc((void **)&c->d_row_info, info.size() * sizeof(uint2)));
-	TRY(hipMemcpy(c->d_row_info, info.data(), info.size() * sizeof(uint2), hipMemcpyHostToDevice));
-	TRY(hipMalloc((void **)&c->d_counts, (2 * (size_t)n + 2) * sizeof(uint32_t)));
-	TRY(hipMemset(c->d_counts, 0, (2 * (size_t)n + 2) * sizeof(uint32_t)));
-	TRY(hipMalloc((void **)&c->d_flags, sizeof(uint32_t)));
-	TRY(hipMemset(c->d_flags, 0, sizeof(uint32_t)));
-	TRY(hipMalloc((void **)&c->d_long_n, sizeof(uint32_t)));
-	TRY(hipMemset(c->d_long_n, 0, sizeof(uint32_t)));
-	TRY(hipEventCreate(&c->t0));
-	TRY(hipEventCreate(&c->t1));
-#undef TRY
-	if (c->stage.init() != VC_OK) {
+	HIPCK(c->d_row_key.upload(keys.data(), keys.size()));
+	HIPCK(c->d_row_info.upload(info.data(), info.size()));
+	HIPCK(c->d_counts.alloc(2 * (size_t)n + 2));
+	HIPCK(c->d_counts.zero());
+	HIPCK(c->d_flags.alloc(1));
+	HIPCK(c->d_flags.zero());
+	HIPCK(c->d_long_n.alloc(1));
+	HIPCK(c->d_long_n.zero());
+	return VC_OK;
+}
+
+} // namespace
+
+extern "C" int vc_bam_create(vc_bam **out, const vc_patterns *db, const char *const *ref_names, int n_refs, int device)
+{
+	if (!out || !db || n_refs < 0 || (n_refs && !ref_names)) return VC_EINVAL;
+	*out = nullptr;
+	const int n = vc_patterns_count(db);
+	if (n > (0x7FFFFFFF >> 1)) return VC_ETOOMANY;
+	vc_bam *c = new (std::nothrow) vc_bam;
+	if (!c) return VC_ENOMEM;
+	c->n_pat = (uint32_t)n;
+	int rc = c->open(device);
+	if (rc == VC_OK) rc = bam_fill(c, db, ref_names, n_refs);
+	if (rc != VC_OK) {
 		vc_bam_destroy(c);
-		return VC_EHIP;
+		return rc;
 	}
 	*out = c;
 	return VC_OK;
@@ -414,21 +378,7 @@ extern "C" int vc_bam_create(vc_bam **out, const vc_patterns *db, const char *co
 extern "C" void vc_bam_destroy(vc_bam *c)
 {
 	if (!c) return;
-	(void)hipSetDevice(c->dev);
-	if (c->st) (void)hipStreamSynchronize(c->st);
-	c->stage.destroy();
-	if (c->d_row_key) (void)hipFree(c->d_row_key);
-	if (c->d_row_info) (void)hipFree(c->d_row_info);
-	if (c->d_counts) (void)hipFree(c->d_counts);
-	if (c->d_flags) (void)hipFree(c->d_flags);
-	if (c->d_reg_s) (void)hipFree(c->d_reg_s);
-	if (c->d_reg_e) (void)hipFree(c->d_reg_e);
-	if (c->d_long_list) (void)hipFree(c->d_long_list);
-	if (c->d_long_n) (void)hipFree(c->d_long_n);
-	if (c->t0) (void)hipEventDestroy(c->t0);
-	if (c->t1) (void)hipEventDestroy(c->t1);
-	c->bridge.destroy();
-	if (c->st) (void)hipStreamDestroy(c->st);
+	c->close();
 	delete c;
 }
 
@@ -446,15 +396,7 @@ extern "C" int vc_bam_set_regions(vc_bam *c, const int32_t *tid, const int32_t *
 	std::sort(e.begin(), e.end());
 	HIPCK(hipSetDevice(c->dev));
 	HIPCK(hipStreamSynchronize(c->st));   // earlier batches read the arrays about to change
-	if (n > c->reg_cap) {
-		if (c->d_reg_s) HIPCK(hipFree(c->d_reg_s));
-		if (c->d_reg_e) HIPCK(hipFree(c->d_reg_e));
-		c->d_reg_s = c->d_reg_e = nullptr;
-		c->reg_cap = 0;
-		HIPCK(hipMalloc((void **)&c->d_reg_s, n * sizeof(uint64_t)));
-		HIPCK(hipMalloc((void **)&c->d_reg_e, n * sizeof(uint64_t)));
-		c->reg_cap = n;
-	}
+	if (n > c->d_reg_s.cap) HIPCK(c->d_reg_s.grow(n, c->d_reg_e, n));
 	if (n) {
 		HIPCK(hipMemcpy(c->d_reg_s, s.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
 		HIPCK(hipMemcpy(c->d_reg_e, e.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
@@ -471,8 +413,7 @@ extern "C" int vc_bam_count_block(vc_bam *c, const vc_bam_rec *recs, uint64_t n_
 	HIPCK(hipSetDevice(c->dev));
 	const size_t rec_bytes = (size_t)n_recs * sizeof(vc_bam_rec), total = rec_bytes + data_bytes;
 	VcSlot *s;
-	int rc = c->stage.acquire(&s);
-	if (rc == VC_OK) rc = vc_slot_reserve(*s, total, 1);
+	const int rc = c->stage.acquire_for(total, 1, &s);
 	if (rc != VC_OK) return rc;
 	// descriptors first, the data behind them: both keep their alignment
 	memcpy(s->h_seq, recs, rec_bytes);
@@ -488,11 +429,7 @@ extern "C" int vc_bam_count_device(vc_bam *c, const vc_bam_rec *d_recs, uint64_t
 	if (!c || (n_recs && !d_recs) || (data_bytes && !d_data)) return VC_EINVAL;
 	if (n_recs == 0) return VC_OK;
 	HIPCK(hipSetDevice(c->dev));
-	const hipStream_t st = stream == VC_STREAM_CTX ? c->st : (hipStream_t)stream;
-	int rc = c->bridge.enter(c->st, st);
-	if (rc == VC_OK) rc = launch(c, d_recs, n_recs, d_data, data_bytes, st);
-	if (rc == VC_OK) rc = c->bridge.leave(c->st, st);
-	return rc;
+	return c->on_stream(stream, [&](hipStream_t st) { return launch(c, d_recs, n_recs, d_data, data_bytes, st); });
 }
 
 extern "C" int vc_bam_finish(vc_bam *c, uint32_t *counts)
@@ -516,8 +453,8 @@ extern "C" int vc_bam_reset(vc_bam *c)
 {
 	if (!c) return VC_EINVAL;
 	HIPCK(hipSetDevice(c->dev));
-	HIPCK(hipMemsetAsync(c->d_counts, 0, (2 * (size_t)c->n_pat + 2) * sizeof(uint32_t), c->st));
-	HIPCK(hipMemsetAsync(c->d_flags, 0, sizeof(uint32_t), c->st));
+	HIPCK(c->d_counts.zero_async(c->st));
+	HIPCK(c->d_flags.zero_async(c->st));
 	return VC_OK;
 }
 
@@ -542,10 +479,7 @@ extern "C" int vc_bam_set_long_threshold(vc_bam *c, uint32_t ops)
 
 extern "C" int vc_bam_kernel_ms(vc_bam *c, float *ms)
 {
-	if (!c || !ms || !c->timed) return VC_EINVAL;
-	HIPCK(hipEventSynchronize(c->t1));
-	HIPCK(hipEventElapsedTime(ms, c->t0, c->t1));
-	return VC_OK;
+	return c ? c->timer.ms(ms) : VC_EINVAL;
 }
 
 extern "C" int vc_bam_count_file(vc_bam *c, const char *path, int n_threads, vc_file_stats *stats)

@@ -50,6 +50,7 @@
 #include <vector>
 
 #include "vafc.h"
+#include "vafc_device.h"
 
 #define CORR_CAP 100000   // correlation-matrix.c:8 MAX_SNPS
 #define CORR_LINE 4096    // correlation-matrix.c:9 MAX_LINE
@@ -396,14 +397,6 @@ extern "C" int vc_vafset_add_arrays(vc_vafset *s, const char *name, const double
 // the matrix
 // ---------------------------------------------------------------------------
 
-#define CCK(x)                                   \
-	do {                                         \
-		if ((x) != hipSuccess) {                 \
-			rc = VC_EHIP;                        \
-			goto done;                           \
-		}                                        \
-	} while (0)
-
 // The x86 NaN of an operation whose first operand is a (see x86_nan above);
 // this host is x86-64, so a NaN from two non-NaN operands is already the
 // default one -- only the choice between two NaN operands is pinned here.
@@ -463,44 +456,47 @@ extern "C" int vc_corr_matrix_raw(const double *vaf, const int32_t *depth, const
 	}
 	std::vector<int> hc(nn, 0);
 	std::vector<double> hs(3 * nn, 0.0);
-	int rc = VC_OK;
-	CorrArgs A{};
-	hipEvent_t e0 = nullptr, e1 = nullptr;
-	void *dbuf[9] = {}, *dpairs = nullptr;
+	// the locals below release what they hold on every return
+	VcTimer timer;
+	VcDevBuf<double> dx, dsum[5];   // sums: sx, sy, sxy, sxx, syy
+	VcDevBuf<uint32_t> dlo, dhi;
+	VcDevBuf<int> dcnt;
+	VcDevBuf<int2> dpairs;
 	std::vector<int2> nanp;
-	CCK(hipSetDevice(device));
-	CCK(hipMalloc(&dbuf[0], hx.size() * sizeof(double)));
-	CCK(hipMalloc(&dbuf[1], hlo.size() * sizeof(uint32_t)));
-	CCK(hipMalloc(&dbuf[2], hhi.size() * sizeof(uint32_t)));
-	CCK(hipMalloc(&dbuf[3], nn * sizeof(int)));
-	for (int i = 4; i < 9; ++i) CCK(hipMalloc(&dbuf[i], nn * sizeof(double)));
-	CCK(hipMemcpy(dbuf[0], hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
-	CCK(hipMemcpy(dbuf[1], hlo.data(), hlo.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	CCK(hipMemcpy(dbuf[2], hhi.data(), hhi.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	A.x = (const double *)dbuf[0];
-	A.lo = (const uint32_t *)dbuf[1];
-	A.hi = (const uint32_t *)dbuf[2];
+	HIPCK(hipSetDevice(device));
+	HIPCK(dx.alloc(hx.size()));
+	HIPCK(dlo.alloc(hlo.size()));
+	HIPCK(dhi.alloc(hhi.size()));
+	HIPCK(dcnt.alloc(nn));
+	for (VcDevBuf<double> &b : dsum) HIPCK(b.alloc(nn));
+	HIPCK(hipMemcpy(dx, hx.data(), dx.bytes(), hipMemcpyHostToDevice));
+	HIPCK(hipMemcpy(dlo, hlo.data(), dlo.bytes(), hipMemcpyHostToDevice));
+	HIPCK(hipMemcpy(dhi, hhi.data(), dhi.bytes(), hipMemcpyHostToDevice));
+	CorrArgs A{};
+	A.x = dx;
+	A.lo = dlo;
+	A.hi = dhi;
 	A.n = n;
 	A.P = P;
 	A.words = words;
-	A.cnt = (int *)dbuf[3];
-	A.sx = (double *)dbuf[4];
-	A.sy = (double *)dbuf[5];
-	A.sxy = (double *)dbuf[6];
-	A.sxx = (double *)dbuf[7];
-	A.syy = (double *)dbuf[8];
-	CCK(hipEventCreate(&e0));
-	CCK(hipEventCreate(&e1));
-	CCK(hipEventRecord(e0, 0));
+	A.cnt = dcnt;
+	A.sx = dsum[0];
+	A.sy = dsum[1];
+	A.sxy = dsum[2];
+	A.sxx = dsum[3];
+	A.syy = dsum[4];
+	HIPCK(timer.init());
+	HIPCK(timer.begin(0));
 	hipLaunchKernelGGL(corr_pairs_kernel, dim3((n + TB - 1) / TB, (n + TA - 1) / TA), dim3(NT), 0, 0, A);
-	CCK(hipGetLastError());
-	CCK(hipEventRecord(e1, 0));
-	CCK(hipEventSynchronize(e1));
-	if (kernel_ms) CCK(hipEventElapsedTime(kernel_ms, e0, e1));
-	CCK(hipMemcpy(hc.data(), A.cnt, nn * sizeof(int), hipMemcpyDeviceToHost));
-	CCK(hipMemcpy(hs.data(), A.sxy, nn * sizeof(double), hipMemcpyDeviceToHost));
-	CCK(hipMemcpy(hs.data() + nn, A.sxx, nn * sizeof(double), hipMemcpyDeviceToHost));
-	CCK(hipMemcpy(hs.data() + 2 * nn, A.syy, nn * sizeof(double), hipMemcpyDeviceToHost));
+	HIPCK(hipGetLastError());
+	HIPCK(timer.end(0));
+	float ms = 0.f;
+	if (timer.ms(&ms) != VC_OK) return VC_EHIP;
+	if (kernel_ms) *kernel_ms = ms;
+	HIPCK(hipMemcpy(hc.data(), A.cnt, nn * sizeof(int), hipMemcpyDeviceToHost));
+	HIPCK(hipMemcpy(hs.data(), A.sxy, nn * sizeof(double), hipMemcpyDeviceToHost));
+	HIPCK(hipMemcpy(hs.data() + nn, A.sxx, nn * sizeof(double), hipMemcpyDeviceToHost));
+	HIPCK(hipMemcpy(hs.data() + 2 * nn, A.syy, nn * sizeof(double), hipMemcpyDeviceToHost));
 	for (int i = 0; i < n; ++i)
 		for (int j = i + 1; j < n; ++j) {
 			const size_t o = (size_t)i * n + j;
@@ -508,14 +504,13 @@ extern "C" int vc_corr_matrix_raw(const double *vaf, const int32_t *depth, const
 				nanp.push_back(make_int2(i, j));
 		}
 	if (!nanp.empty()) {
-		CCK(hipMalloc(&dpairs, nanp.size() * sizeof(int2)));
-		CCK(hipMemcpy(dpairs, nanp.data(), nanp.size() * sizeof(int2), hipMemcpyHostToDevice));
+		HIPCK(dpairs.upload(nanp.data(), nanp.size()));
 		hipLaunchKernelGGL(corr_pairs_x86_kernel, dim3(((int)nanp.size() + 63) / 64), dim3(64), 0, 0, A,
 		                   (const int2 *)dpairs, (int)nanp.size());
-		CCK(hipGetLastError());
-		CCK(hipMemcpy(hs.data(), A.sxy, nn * sizeof(double), hipMemcpyDeviceToHost));
-		CCK(hipMemcpy(hs.data() + nn, A.sxx, nn * sizeof(double), hipMemcpyDeviceToHost));
-		CCK(hipMemcpy(hs.data() + 2 * nn, A.syy, nn * sizeof(double), hipMemcpyDeviceToHost));
+		HIPCK(hipGetLastError());
+		HIPCK(hipMemcpy(hs.data(), A.sxy, nn * sizeof(double), hipMemcpyDeviceToHost));
+		HIPCK(hipMemcpy(hs.data() + nn, A.sxx, nn * sizeof(double), hipMemcpyDeviceToHost));
+		HIPCK(hipMemcpy(hs.data() + 2 * nn, A.syy, nn * sizeof(double), hipMemcpyDeviceToHost));
 	}
 	for (int i = 0; i < n; ++i)
 		for (int j = i + 1; j < n; ++j) {
@@ -524,13 +519,7 @@ extern "C" int vc_corr_matrix_raw(const double *vaf, const int32_t *depth, const
 			corr[o] = r;
 			corr[(size_t)j * n + i] = r;                       // :160
 		}
-done:
-	for (void *p : dbuf)
-		if (p) (void)hipFree(p);
-	if (dpairs) (void)hipFree(dpairs);
-	if (e0) (void)hipEventDestroy(e0);
-	if (e1) (void)hipEventDestroy(e1);
-	return rc;
+	return VC_OK;
 }
 
 extern "C" int vc_corr_matrix(const vc_vafset *s, int min_snps, int min_depth, double *corr, int device,

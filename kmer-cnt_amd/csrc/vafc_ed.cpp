@@ -34,9 +34,8 @@ struct EdWidth {
 	uint32_t n_groups = 0;
 	int waves = 1;
 	int lds_masks = 1;
-	void *d_masks = nullptr;
-	uint32_t *d_qlen = nullptr;
-	uint32_t *d_qout = nullptr;
+	VcDevBuf<uint8_t> d_masks;
+	VcDevBuf<uint32_t> d_qlen, d_qout;
 };
 
 // batches of vc_ed_count_file: bytes ($VAFC_BATCH_BYTES: vc_batch_bytes) and reads per pinned slot
@@ -45,22 +44,15 @@ const size_t ED_BATCH_READS = (size_t)1 << 18;
 
 } // namespace
 
-struct vc_ed {
-	int dev = 0;
+struct vc_ed : VcDevice {
 	int max_edit = 0;
-	int n_cu = 256;
 	uint32_t n_out = 0;       // counts
 	uint32_t n_class = 0;
-	hipStream_t st = nullptr;
-	uint8_t *d_cls = nullptr;
-	uint32_t *d_counts = nullptr;
-	uint32_t *d_flags = nullptr;
+	VcDevBuf<uint8_t> d_cls;
+	VcDevBuf<uint32_t> d_counts;   // n_out + 2
+	VcDevBuf<uint32_t> d_flags;
 	EdWidth width[VC_ED_WIDTHS];
-	VcStager stage;
-	hipEvent_t t0 = nullptr, t1 = nullptr;
-	bool timed = false;
 	uint32_t max_ranges = 0;   // vc_ed_set_max_ranges: 0 = sized from the device
-	VcStreamBridge bridge;     // vc_ed_count_device on a caller's stream
 
 	int submit(size_t bytes, uint64_t n_reads);   // the acquired slot of `stage`: H2D copies + kernels
 };
@@ -72,7 +64,7 @@ int launch(vc_ed *c, const uint8_t *d_seq, size_t seq_bytes, const uint64_t *d_o
            uint64_t n_reads, hipStream_t st)
 {
 	if (n_reads == 0) return VC_OK;
-	HIPCK(hipEventRecord(c->t0, st));
+	HIPCK(c->timer.begin(st));
 	for (int w = 0; w < VC_ED_WIDTHS; ++w) {
 		const EdWidth &E = c->width[w];
 		if (E.n_groups == 0) continue;
@@ -104,8 +96,7 @@ int launch(vc_ed *c, const uint8_t *d_seq, size_t seq_bytes, const uint64_t *d_o
 		gy = (n_reads + A.reads_per_range - 1) / A.reads_per_range;
 		HIPCK(vc_ed_launch(&A, w, E.waves, E.lds_masks, (unsigned)gx, (unsigned)gy, st));
 	}
-	HIPCK(hipEventRecord(c->t1, st));
-	c->timed = true;
+	HIPCK(c->timer.end(st));
 	return VC_OK;
 }
 
@@ -114,26 +105,10 @@ template <typename W> void set_bit(std::vector<uint8_t> &tab, size_t word, unsig
 	reinterpret_cast<W *>(tab.data())[word] |= (W)1 << bit;
 }
 
-// Build the device data of a handle.  q: the query bytes, query i at
+// Build the device data of an open handle.  q: the query bytes, query i at
 // offs[i] of length lens[i] (1..127), its count at out[i].
-int ed_build(vc_ed **outp, const uint8_t *q, const uint32_t *offs, const uint32_t *lens, const uint32_t *out,
-             size_t n, uint32_t n_out, int max_edit, int device)
+int ed_fill(vc_ed *c, const uint8_t *q, const uint32_t *offs, const uint32_t *lens, const uint32_t *out, size_t n)
 {
-	for (size_t i = 0; i < n; ++i)
-		if (lens[i] < 1 || lens[i] > 127) return VC_EINVAL;
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VC_ENODEV;
-	if (device < 0 || device >= ndev) return VC_EINVAL;
-	HIPCK(hipSetDevice(device));
-	vc_ed *c = new (std::nothrow) vc_ed;
-	if (!c) return VC_ENOMEM;
-	c->dev = device;
-	c->max_edit = max_edit;
-	c->n_out = n_out;
-	hipDeviceProp_t prop;
-	if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-		c->n_cu = prop.multiProcessorCount;
-
 	// symbol classes: one per byte value that occurs in a query, and class 0
 	// for every other byte (no bit of any mask set); with all 256 values in
 	// use there is no other byte and class = byte
@@ -151,30 +126,11 @@ int ed_build(vc_ed **outp, const uint8_t *q, const uint32_t *offs, const uint32_
 		for (int b = 0; b < 256; ++b) cls[b] = used[b] ? (uint8_t)next++ : (uint8_t)0;
 		c->n_class = (uint32_t)next;
 	}
-
-#define TRY(call)                                                                                  \
-	do {                                                                                           \
-		hipError_t e_ = (call);                                                                    \
-		if (e_ != hipSuccess) {                                                                    \
-			fprintf(stderr, "[E::vafc] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_),     \
-			        __FILE__, __LINE__);                                                           \
-			vc_ed_destroy(c);                                                                      \
-			return VC_EHIP;                                                                        \
-		}                                                                                          \
-	} while (0)
-	TRY(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
-	TRY(hipMalloc((void **)&c->d_cls, 256));
-	TRY(hipMemcpy(c->d_cls, cls, 256, hipMemcpyHostToDevice));
-	TRY(hipMalloc((void **)&c->d_counts, ((size_t)n_out + 2) * sizeof(uint32_t)));
-	TRY(hipMemset(c->d_counts, 0, ((size_t)n_out + 2) * sizeof(uint32_t)));
-	TRY(hipMalloc((void **)&c->d_flags, sizeof(uint32_t)));
-	TRY(hipMemset(c->d_flags, 0, sizeof(uint32_t)));
-	TRY(hipEventCreate(&c->t0));
-	TRY(hipEventCreate(&c->t1));
-	if (c->stage.init() != VC_OK) {
-		vc_ed_destroy(c);
-		return VC_EHIP;
-	}
+	HIPCK(c->d_cls.upload(cls, 256));
+	HIPCK(c->d_counts.alloc((size_t)c->n_out + 2));
+	HIPCK(c->d_counts.zero());
+	HIPCK(c->d_flags.alloc(1));
+	HIPCK(c->d_flags.zero());
 
 	for (int w = 0; w < VC_ED_WIDTHS; ++w) {
 		const uint32_t lo = w == VC_ED_W32 ? 1 : (w == VC_ED_W64 ? 33 : 65);
@@ -204,14 +160,29 @@ int ed_build(vc_ed **outp, const uint8_t *q, const uint32_t *offs, const uint32_
 				else set_bit<uint64_t>(tab, word, j % bits);
 			}
 		}
-		TRY(hipMalloc(&E.d_masks, tab.size()));
-		TRY(hipMemcpy(E.d_masks, tab.data(), tab.size(), hipMemcpyHostToDevice));
-		TRY(hipMalloc((void **)&E.d_qlen, lanes * sizeof(uint32_t)));
-		TRY(hipMemcpy(E.d_qlen, qlen.data(), lanes * sizeof(uint32_t), hipMemcpyHostToDevice));
-		TRY(hipMalloc((void **)&E.d_qout, lanes * sizeof(uint32_t)));
-		TRY(hipMemcpy(E.d_qout, qout.data(), lanes * sizeof(uint32_t), hipMemcpyHostToDevice));
+		HIPCK(E.d_masks.upload(tab.data(), tab.size()));
+		HIPCK(E.d_qlen.upload(qlen.data(), lanes));
+		HIPCK(E.d_qout.upload(qout.data(), lanes));
 	}
-#undef TRY
+	return VC_OK;
+}
+
+// A new handle for n checked queries; a failed step returns through vc_ed_destroy.
+int ed_build(vc_ed **outp, const uint8_t *q, const uint32_t *offs, const uint32_t *lens, const uint32_t *out,
+             size_t n, uint32_t n_out, int max_edit, int device)
+{
+	for (size_t i = 0; i < n; ++i)
+		if (lens[i] < 1 || lens[i] > 127) return VC_EINVAL;
+	vc_ed *c = new (std::nothrow) vc_ed;
+	if (!c) return VC_ENOMEM;
+	c->max_edit = max_edit;
+	c->n_out = n_out;
+	int rc = c->open(device);
+	if (rc == VC_OK) rc = ed_fill(c, q, offs, lens, out, n);
+	if (rc != VC_OK) {
+		vc_ed_destroy(c);
+		return rc;
+	}
 	*outp = c;
 	return VC_OK;
 }
@@ -267,21 +238,7 @@ extern "C" int vc_ed_create(vc_ed **out, const vc_patterns *db, int max_edit, in
 extern "C" void vc_ed_destroy(vc_ed *c)
 {
 	if (!c) return;
-	(void)hipSetDevice(c->dev);
-	if (c->st) (void)hipStreamSynchronize(c->st);
-	c->stage.destroy();
-	for (EdWidth &E : c->width) {
-		if (E.d_masks) (void)hipFree(E.d_masks);
-		if (E.d_qlen) (void)hipFree(E.d_qlen);
-		if (E.d_qout) (void)hipFree(E.d_qout);
-	}
-	if (c->d_cls) (void)hipFree(c->d_cls);
-	if (c->d_counts) (void)hipFree(c->d_counts);
-	if (c->d_flags) (void)hipFree(c->d_flags);
-	if (c->t0) (void)hipEventDestroy(c->t0);
-	if (c->t1) (void)hipEventDestroy(c->t1);
-	c->bridge.destroy();
-	if (c->st) (void)hipStreamDestroy(c->st);
+	c->close();
 	delete c;
 }
 
@@ -294,8 +251,7 @@ extern "C" int vc_ed_count_block(vc_ed *c, const uint8_t *seq, size_t seq_bytes,
 		if (offs[i] > seq_bytes || lens[i] > seq_bytes - offs[i]) return VC_EINVAL;
 	HIPCK(hipSetDevice(c->dev));
 	VcSlot *s;
-	int rc = c->stage.acquire(&s);
-	if (rc == VC_OK) rc = vc_slot_reserve(*s, seq_bytes, n_reads);
+	const int rc = c->stage.acquire_for(seq_bytes, n_reads, &s);
 	if (rc != VC_OK) return rc;
 	if (seq_bytes) memcpy(s->h_seq, seq, seq_bytes);
 	memcpy(s->h_offs, offs, n_reads * sizeof(uint64_t));
@@ -309,11 +265,7 @@ extern "C" int vc_ed_count_device(vc_ed *c, const uint8_t *d_seq, size_t seq_byt
 	if (!c || (n_reads && (!d_offs || !d_lens)) || (seq_bytes && !d_seq)) return VC_EINVAL;
 	if (n_reads == 0) return VC_OK;
 	HIPCK(hipSetDevice(c->dev));
-	const hipStream_t st = stream == VC_STREAM_CTX ? c->st : (hipStream_t)stream;
-	int rc = c->bridge.enter(c->st, st);
-	if (rc == VC_OK) rc = launch(c, d_seq, seq_bytes, d_offs, d_lens, n_reads, st);
-	if (rc == VC_OK) rc = c->bridge.leave(c->st, st);
-	return rc;
+	return c->on_stream(stream, [&](hipStream_t st) { return launch(c, d_seq, seq_bytes, d_offs, d_lens, n_reads, st); });
 }
 
 extern "C" int vc_ed_finish(vc_ed *c, uint32_t *counts)
@@ -337,8 +289,8 @@ extern "C" int vc_ed_reset(vc_ed *c)
 {
 	if (!c) return VC_EINVAL;
 	HIPCK(hipSetDevice(c->dev));
-	HIPCK(hipMemsetAsync(c->d_counts, 0, ((size_t)c->n_out + 2) * sizeof(uint32_t), c->st));
-	HIPCK(hipMemsetAsync(c->d_flags, 0, sizeof(uint32_t), c->st));
+	HIPCK(c->d_counts.zero_async(c->st));
+	HIPCK(c->d_flags.zero_async(c->st));
 	return VC_OK;
 }
 
@@ -363,10 +315,7 @@ extern "C" int vc_ed_set_max_ranges(vc_ed *c, uint32_t max_ranges)
 
 extern "C" int vc_ed_kernel_ms(vc_ed *c, float *ms)
 {
-	if (!c || !ms || !c->timed) return VC_EINVAL;
-	HIPCK(hipEventSynchronize(c->t1));
-	HIPCK(hipEventElapsedTime(ms, c->t0, c->t1));
-	return VC_OK;
+	return c ? c->timer.ms(ms) : VC_EINVAL;
 }
 
 extern "C" int vc_ed_count_file(vc_ed *c, const char *path, int n_threads, vc_file_stats *stats)

@@ -44,20 +44,19 @@
 // device context
 // ---------------------------------------------------------------------------
 
-struct vc_ctx {
-	int dev = 0, k = 21;
+// The core's `stage` takes the host batches (vc_count_block, the sequential file pass).
+struct vc_ctx : VcDevice {
+	int k = 21;
 	uint32_t n_patterns = 0;
 	uint64_t n_keys = 0;
-	hipStream_t st = nullptr;
-	int n_cu = 256;
-	vc_slot_t *d_table = nullptr;
+	VcDevBuf<vc_slot_t> d_table;
 	int ablate = 0;                   // kernel ablation variant (libvafc_abl.so only)
 	uint32_t variant = 0;             // kernel A/B experiment knobs ($VAFC_VARIANT, tools/ab.py)
 	int nt4 = 0;                      // seq_nt4 decode everywhere (vc_set_nt4_decode)
 	uint32_t tbits = 0;
-	uint32_t *d_filter = nullptr;
+	VcDevBuf<uint32_t> d_filter;
 	uint32_t wbits = 0;
-	uint32_t *d_l2f = nullptr;             // second-level filter (large key sets only)
+	VcDevBuf<uint32_t> d_l2f;              // second-level filter (large key sets only)
 	uint32_t l2bits = 0;
 	uint32_t fsh = 0;
 	uint32_t flank = 0;                    // the filter is the flank bitmap (vafc_common.h)
@@ -66,20 +65,16 @@ struct vc_ctx {
 	uint32_t qcap = VC_QCAP;               // LDS queue entries per wave
 	uint32_t *d_counts = nullptr;          // active outputs (own or bound)
 	unsigned long long *d_tally = nullptr;
-	uint32_t *own_counts = nullptr;
-	unsigned long long *own_tally = nullptr;
-	uint32_t *d_nlong = nullptr;
-	uint32_t *d_flags = nullptr;           // kernel error flags (VcKernelArgs::flags)
-	uint8_t *d_pad = nullptr;              // 64 B staging for inputs under 16 B (kernels load 16 B)
-	uint32_t *d_long = nullptr;
-	uint32_t long_cap = 0;
-	VcStager stage;                        // host batches (vc_count_block, the sequential file pass)
+	VcDevBuf<uint32_t> own_counts;         // 2 * n_patterns + 2
+	VcDevBuf<unsigned long long> own_tally;
+	VcDevBuf<uint32_t> d_nlong;
+	VcDevBuf<uint32_t> d_flags;            // kernel error flags (VcKernelArgs::flags)
+	VcDevBuf<uint8_t> d_pad;               // 64 B staging for inputs under 16 B (kernels load 16 B)
+	VcDevBuf<uint32_t> d_long;             // the long-read list (ensure_long_cap)
 	std::vector<VcSlot> islot;             // parallel ingest (vc_count_file on plain files)
 	hipStream_t cst = nullptr;             // the parallel reader's H2D copies (created on first use)
 	bool ingest_warm = false;              // a parallel-reader pass has completed: its slots are pinned
-	bool timing = false, timed = false;
-	hipEvent_t t0 = nullptr, t1 = nullptr;
-	VcStreamBridge bridge;            // vc_count_device on a stream other than st
+	bool timing = false;              // vc_set_timing: the timer records only while this is on
 	VcCpuSet cpus;                    // the GPUs' NUMA-node CPUs for the reader threads (gpu_cpus)
 	int cpus_threads = -1;            // the thread count cpus was computed for
 	struct Kc *kc = nullptr;               // histogram mode (vc_kc_create)
@@ -101,16 +96,15 @@ static inline vc_ctx *next_shard(vc_ctx *c) { return shard_at(c, (int)(c->rr++ %
 
 // kc-c4 histogram mode: the device hash table and its bookkeeping
 struct Kc {
-	unsigned long long *d_table = nullptr;   // 2 * slots
+	VcDevBuf<unsigned long long> d_table;    // 2 * slots
 	uint64_t slots = 0;
 	uint32_t tbits = 0;
 	uint32_t n_parts = 1, part = 0;
-	unsigned long long *d_stats = nullptr;   // k-mers, distinct, table full, long-read list full
-	unsigned long long *d_hist = nullptr;    // up to 1024 bins + the slots counted
-	uint32_t *d_nlong = nullptr, *d_long = nullptr;
-	uint64_t *d_segstart = nullptr;
-	uint32_t long_cap = 0;
-	uint64_t *d_first = nullptr;             // first-occurrence stamps (vc_kc_track_first)
+	VcDevBuf<unsigned long long> d_stats;    // k-mers, distinct, table full, long-read list full
+	VcDevBuf<unsigned long long> d_hist;     // up to 1024 bins + the slots counted
+	VcDevBuf<uint32_t> d_nlong, d_long;      // d_long: the long-read list, d_long.cap entries
+	VcDevBuf<uint64_t> d_segstart;           // d_long.cap + 1, grown with d_long
+	VcDevBuf<uint64_t> d_first;              // first-occurrence stamps (vc_kc_track_first)
 	bool track_first = false, lookup_only = false;
 	uint64_t read_base = 0;                  // reads launched since the last reset
 };
@@ -118,35 +112,19 @@ struct Kc {
 static int ensure_long_cap(vc_ctx *c, uint64_t seq_bytes)
 {
 	uint64_t need = seq_bytes / (VC_LONG_READ + 1) + 1;
-	if (need <= c->long_cap) return VC_OK;
+	if (need <= c->d_long.cap) return VC_OK;
 	if (need > 0xFFFFFFFFull) need = 0xFFFFFFFFull;
 	HIPCK(hipStreamSynchronize(c->st));
-	if (c->d_long) HIPCK(hipFree(c->d_long));
-	c->d_long = nullptr;
-	HIPCK(hipMalloc(&c->d_long, need * sizeof(uint32_t)));
-	c->long_cap = (uint32_t)need;
+	HIPCK(c->d_long.grow(need));
 	return VC_OK;
 }
 
-extern "C" int vc_create(vc_ctx **out, int k, const uint64_t *keys, const uint32_t *vals,
-                         size_t n_keys, uint32_t n_patterns, int device)
+// The key table, the filters and the outputs of an open context.
+static int ctx_fill(vc_ctx *c, const uint64_t *keys, const uint32_t *vals, size_t n_keys)
 {
-	if (!out || k < 1 || k > 31 || (n_keys && (!keys || !vals))) return VC_EINVAL;
-	*out = nullptr;
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VC_ENODEV;
-	if (device < 0 || device >= ndev) return VC_EINVAL;
-	HIPCK(hipSetDevice(device));
+	const int k = c->k;
+	const uint32_t n_patterns = c->n_patterns;
 	HIPCK(vc_kernel_setup());
-
-	vc_ctx *c = new (std::nothrow) vc_ctx;
-	if (!c) return VC_ENOMEM;
-	c->dev = device;
-	c->k = k;
-	c->n_patterns = n_patterns;
-	hipDeviceProp_t prop;
-	if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-		c->n_cu = prop.multiProcessorCount;
 
 	// exact table: 16-byte {key, value} slots, linear probing, load <= 1/2
 	uint32_t tbits = 4;
@@ -242,46 +220,40 @@ extern "C" int vc_create(vc_ctx **out, int k, const uint64_t *keys, const uint32
 	c->ablate = getenv("VAFC_ABLATE") ? atoi(getenv("VAFC_ABLATE")) : 0;
 	c->variant = getenv("VAFC_VARIANT") ? (uint32_t)atoi(getenv("VAFC_VARIANT")) : 0u;
 
-	int rc = VC_OK;
-#define TRY(call)                                                                        \
-	do {                                                                                 \
-		hipError_t e_ = (call);                                                          \
-		if (e_ != hipSuccess) {                                                          \
-			fprintf(stderr, "[E::vafc] %s failed: %s\n", #call, hipGetErrorString(e_)); \
-			rc = VC_EHIP;                                                                \
-			goto fail;                                                                   \
-		}                                                                                \
-	} while (0)
-	TRY(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
-	TRY(hipMalloc(&c->d_table, tslots * sizeof(vc_slot_t)));
-	TRY(hipMalloc(&c->d_filter, fw.size() * sizeof(uint32_t)));
-	TRY(hipMalloc(&c->own_counts, (2 * (size_t)n_patterns + 2) * sizeof(uint32_t)));
-	TRY(hipMalloc(&c->own_tally, sizeof(unsigned long long)));
+	HIPCK(c->d_table.upload(tab.data(), tslots));
+	HIPCK(c->d_filter.upload(fw.data(), fw.size()));
+	HIPCK(c->own_counts.alloc(2 * (size_t)n_patterns + 2));
+	HIPCK(c->own_counts.zero());
+	HIPCK(c->own_tally.alloc(1));
+	HIPCK(c->own_tally.zero());
 	c->d_counts = c->own_counts;
 	c->d_tally = c->own_tally;
-	TRY(hipMalloc(&c->d_nlong, sizeof(uint32_t)));
-	TRY(hipMalloc(&c->d_flags, sizeof(uint32_t)));
-	TRY(hipMemset(c->d_flags, 0, sizeof(uint32_t)));
-	TRY(hipMalloc(&c->d_pad, 64));
-	TRY(hipMemset(c->d_pad, 0, 64));
-	TRY(hipMemcpy(c->d_table, tab.data(), tslots * sizeof(vc_slot_t), hipMemcpyHostToDevice));
-	TRY(hipMemcpy(c->d_filter, fw.data(), fw.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	if (l2bits) {
-		TRY(hipMalloc(&c->d_l2f, l2w.size() * sizeof(uint32_t)));
-		TRY(hipMemcpy(c->d_l2f, l2w.data(), l2w.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+	HIPCK(c->d_nlong.alloc(1));
+	HIPCK(c->d_flags.alloc(1));
+	HIPCK(c->d_flags.zero());
+	HIPCK(c->d_pad.alloc(64));
+	HIPCK(c->d_pad.zero());
+	if (l2bits) HIPCK(c->d_l2f.upload(l2w.data(), l2w.size()));
+	return ensure_long_cap(c, (uint64_t)1 << 30);
+}
+
+extern "C" int vc_create(vc_ctx **out, int k, const uint64_t *keys, const uint32_t *vals,
+                         size_t n_keys, uint32_t n_patterns, int device)
+{
+	if (!out || k < 1 || k > 31 || (n_keys && (!keys || !vals))) return VC_EINVAL;
+	*out = nullptr;
+	vc_ctx *c = new (std::nothrow) vc_ctx;
+	if (!c) return VC_ENOMEM;
+	c->k = k;
+	c->n_patterns = n_patterns;
+	int rc = c->open(device);
+	if (rc == VC_OK) rc = ctx_fill(c, keys, vals, n_keys);
+	if (rc != VC_OK) {
+		vc_destroy(c);
+		return rc;
 	}
-	TRY(hipMemset(c->d_counts, 0, (2 * (size_t)n_patterns + 2) * sizeof(uint32_t)));
-	TRY(hipMemset(c->d_tally, 0, sizeof(unsigned long long)));
-	TRY(hipEventCreate(&c->t0));
-	TRY(hipEventCreate(&c->t1));
-	if ((rc = c->stage.init()) != VC_OK) goto fail;
-	if ((rc = ensure_long_cap(c, (uint64_t)1 << 30)) != VC_OK) goto fail;
-#undef TRY
 	*out = c;
 	return VC_OK;
-fail:
-	vc_destroy(c);
-	return rc;
 }
 
 static void rccl_comms_destroy(vc_ctx *c);
@@ -292,31 +264,10 @@ extern "C" void vc_destroy(vc_ctx *c)
 	rccl_comms_destroy(c);
 	for (vc_ctx *r : c->rep) vc_destroy(r);
 	c->rep.clear();
-	(void)hipSetDevice(c->dev);
-	if (c->st) (void)hipStreamSynchronize(c->st);
-	c->stage.destroy();
+	c->close();
 	for (VcSlot &s : c->islot) vc_slot_destroy(s);
 	if (c->cst) (void)hipStreamDestroy(c->cst);
-	if (c->t0) (void)hipEventDestroy(c->t0);
-	if (c->t1) (void)hipEventDestroy(c->t1);
-	c->bridge.destroy();
-	if (c->d_table) (void)hipFree(c->d_table);
-	if (c->d_filter) (void)hipFree(c->d_filter);
-	if (c->d_l2f) (void)hipFree(c->d_l2f);
-	if (c->own_counts) (void)hipFree(c->own_counts);
-	if (c->own_tally) (void)hipFree(c->own_tally);
-	if (c->d_nlong) (void)hipFree(c->d_nlong);
-	if (c->d_flags) (void)hipFree(c->d_flags);
-	if (c->d_pad) (void)hipFree(c->d_pad);
-	if (c->d_long) (void)hipFree(c->d_long);
-	if (c->kc) {
-		Kc &K = *c->kc;
-		for (void *q : {(void *)K.d_table, (void *)K.d_stats, (void *)K.d_hist, (void *)K.d_nlong, (void *)K.d_long,
-		                (void *)K.d_segstart, (void *)K.d_first})
-			if (q) (void)hipFree(q);
-		delete c->kc;
-	}
-	if (c->st) (void)hipStreamDestroy(c->st);
+	delete c->kc;
 	delete c;
 }
 
@@ -327,16 +278,10 @@ static int kc_launch(vc_ctx *c, const uint8_t *d_seq, size_t seq_bytes, const ui
 	Kc &K = *c->kc;
 	if (n_reads > 0xFFFFFFFFull) return VC_EINVAL;   // the long-read list holds u32 read indices
 	const uint64_t need = seq_bytes / (KC_LONG + 1) + 1;
-	if (need > K.long_cap) {
+	if (need > K.d_long.cap) {
 		HIPCK(hipStreamSynchronize(st));
-		if (K.d_long) HIPCK(hipFree(K.d_long));
-		if (K.d_segstart) HIPCK(hipFree(K.d_segstart));
-		K.d_long = nullptr;
-		K.d_segstart = nullptr;
 		const uint64_t cap = need < 0xFFFFFFF0ull ? need : 0xFFFFFFF0ull;
-		HIPCK(hipMalloc(&K.d_long, cap * sizeof(uint32_t)));
-		HIPCK(hipMalloc(&K.d_segstart, (cap + 1) * sizeof(uint64_t)));
-		K.long_cap = (uint32_t)cap;
+		HIPCK(K.d_long.grow(cap, K.d_segstart, cap + 1));
 	}
 	KcArgs A;
 	A.seq = d_seq;
@@ -357,17 +302,14 @@ static int kc_launch(vc_ctx *c, const uint8_t *d_seq, size_t seq_bytes, const ui
 	A.stats = K.d_stats;
 	A.nlong = K.d_nlong;
 	A.longlist = K.d_long;
-	A.long_cap = K.long_cap;
+	A.long_cap = (uint32_t)K.d_long.cap;
 	A.segstart = K.d_segstart;
 	const uint64_t blocks = (n_reads + KC_THREADS - 1) / KC_THREADS;
 	const uint64_t maxg = (uint64_t)c->n_cu * 16;
 	const int grid = (int)(blocks < maxg ? blocks : maxg);
-	if (c->timing) HIPCK(hipEventRecord(c->t0, st));
+	if (c->timing) HIPCK(c->timer.begin(st));
 	HIPCK(vc_launch_kc(&A, grid, st));
-	if (c->timing) {
-		HIPCK(hipEventRecord(c->t1, st));
-		c->timed = true;
-	}
+	if (c->timing) HIPCK(c->timer.end(st));
 	return VC_OK;
 }
 
@@ -425,18 +367,15 @@ static int launch(vc_ctx *c, const uint8_t *d_seq, size_t seq_bytes, const uint6
 	A.tally = c->d_tally;
 	A.nlong = c->d_nlong;
 	A.longlist = c->d_long;
-	A.long_cap = c->long_cap;
+	A.long_cap = (uint32_t)c->d_long.cap;
 	A.flags = c->d_flags;
 	uint64_t groups = (n_reads + VC_BLOCK - 1) / VC_BLOCK;
 	int grid = (int)(groups < (uint64_t)c->n_cu ? groups : (uint64_t)c->n_cu);
-	if (may_long) HIPCK(hipMemsetAsync(c->d_nlong, 0, sizeof(uint32_t), st));
-	if (c->timing) HIPCK(hipEventRecord(c->t0, st));
+	if (may_long) HIPCK(c->d_nlong.zero_async(st));
+	if (c->timing) HIPCK(c->timer.begin(st));
 	HIPCK(vc_launch_count(&A, grid, may_long ? c->n_cu : 0, st));
 	if (tiny) HIPCK(hipStreamSynchronize(st));   // d_pad is reused by the next tiny call
-	if (c->timing) {
-		HIPCK(hipEventRecord(c->t1, st));
-		c->timed = true;
-	}
+	if (c->timing) HIPCK(c->timer.end(st));
 	return VC_OK;
 }
 
@@ -470,14 +409,7 @@ extern "C" int vc_count_device(vc_ctx *c, const uint8_t *d_seq, size_t seq_bytes
 		++c->batches;
 	}
 	HIPCK(hipSetDevice(c->dev));
-	// NULL is HIP's null stream (ordered with the legacy default stream, which
-	// is torch's default stream), as for every HIP API; VC_STREAM_CTX is the
-	// counter's own non-blocking stream
-	const hipStream_t st = stream == VC_STREAM_CTX ? c->st : (hipStream_t)stream;
-	int rc = c->bridge.enter(c->st, st);
-	if (rc == VC_OK) rc = launch(c, d_seq, seq_bytes, d_offs, d_lens, n_reads, st);
-	if (rc == VC_OK) rc = c->bridge.leave(c->st, st);
-	return rc;
+	return c->on_stream(stream, [&](hipStream_t st) { return launch(c, d_seq, seq_bytes, d_offs, d_lens, n_reads, st); });
 }
 
 int vc_ctx::submit(size_t bytes, uint64_t n_reads)
@@ -499,8 +431,7 @@ extern "C" int vc_count_block(vc_ctx *c, const uint8_t *seq, size_t seq_bytes, c
 	c = next_shard(c);
 	HIPCK(hipSetDevice(c->dev));
 	VcSlot *s;
-	int rc = c->stage.acquire(&s);
-	if (rc == VC_OK) rc = vc_slot_reserve(*s, seq_bytes, n_reads);
+	const int rc = c->stage.acquire_for(seq_bytes, n_reads, &s);
 	if (rc != VC_OK) return rc;
 	memcpy(s->h_seq, seq, seq_bytes);
 	memcpy(s->h_offs, offs, n_reads * sizeof(uint64_t));
@@ -597,18 +528,11 @@ extern "C" int vc_set_timing(vc_ctx *c, int enable)
 {
 	if (!c) return VC_EINVAL;
 	c->timing = enable != 0;
-	c->timed = false;
+	c->timer.clear();
 	return VC_OK;
 }
 
-extern "C" int vc_kernel_ms(vc_ctx *c, float *ms)
-{
-	if (!c || !ms) return VC_EINVAL;
-	if (!c->timed) return VC_EINVAL;
-	HIPCK(hipEventSynchronize(c->t1));
-	HIPCK(hipEventElapsedTime(ms, c->t0, c->t1));
-	return VC_OK;
-}
+extern "C" int vc_kernel_ms(vc_ctx *c, float *ms) { return c ? c->timer.ms(ms) : VC_EINVAL; }
 
 extern "C" int vc_table_info(const vc_ctx *c, uint64_t *n_keys, uint64_t *slots, uint64_t *filter_bytes)
 {
@@ -1462,8 +1386,8 @@ extern "C" int vc_kc_create(vc_ctx **out, int k, uint64_t table_slots, int devic
 	}
 	K->tbits = tbits;
 	K->slots = (uint64_t)1 << tbits;
-	if (hipMalloc(&K->d_table, K->slots * 16) != hipSuccess || hipMalloc(&K->d_stats, 4 * 8) != hipSuccess ||
-	    hipMalloc(&K->d_hist, 1025 * 8) != hipSuccess || hipMalloc(&K->d_nlong, 4) != hipSuccess) {
+	if (K->d_table.alloc(2 * K->slots) != hipSuccess || K->d_stats.alloc(4) != hipSuccess ||
+	    K->d_hist.alloc(1025) != hipSuccess || K->d_nlong.alloc(1) != hipSuccess) {
 		vc_destroy(c);
 		return VC_EHIP;
 	}
@@ -1537,10 +1461,7 @@ extern "C" int vc_kc_track_first(vc_ctx *c, int on)
 	Kc &K = *c->kc;
 	HIPCK(hipSetDevice(c->dev));
 	HIPCK(hipStreamSynchronize(c->st));
-	if (on && !K.d_first && hipMalloc(&K.d_first, K.slots * 8) != hipSuccess) {
-		K.d_first = nullptr;
-		return VC_ENOMEM;
-	}
+	if (on && !K.d_first && K.d_first.alloc(K.slots) != hipSuccess) return VC_ENOMEM;
 	K.track_first = on != 0;
 	return vc_reset(c);
 }
@@ -1561,6 +1482,7 @@ extern "C" int vc_yak_bloom_select(vc_ctx *c, int pre, int bf_shift, int n_hash)
 	const bool bf_on = n_hash > 0 && bf_shift > pre && ns >= 9 && ns + 9 <= 64;
 	if (bf_on && !K.track_first) return VC_EINVAL;
 	YakBloom B;
+	VcDevBuf<unsigned long long> wtab;   // the scratch table of this call
 	B.table = K.d_table;
 	B.counts_out = K.d_table;
 	B.first = K.d_first;
@@ -1584,14 +1506,15 @@ extern "C" int vc_yak_bloom_select(vc_ctx *c, int pre, int bf_shift, int n_hash)
 		B.wslots = (uint64_t)1 << wbits;
 		// no room for the scratch table: report full, so the caller counts
 		// again in more partitions (fewer singletons per pass)
-		if (hipMalloc(&B.wtab, B.wslots * 16) != hipSuccess) return VC_EFULL;
-		HIPCK(hipMemsetAsync(B.wtab, 0, B.wslots * 16, c->st));
+		if (wtab.alloc(2 * B.wslots) != hipSuccess) return VC_EFULL;
+		B.wtab = wtab;
+		HIPCK(wtab.zero_async(c->st));
 	}
 	const uint64_t blocks = (K.slots + 255) / 256;
 	const uint64_t maxg = (uint64_t)c->n_cu * 8;
 	hipError_t e = vc_launch_yak_select(&B, (int)(blocks < maxg ? blocks : maxg), c->st);
 	if (e == hipSuccess) e = hipStreamSynchronize(c->st);
-	if (B.wtab) (void)hipFree(B.wtab);
+	wtab.free();
 	if (e != hipSuccess) return VC_EHIP;
 	HIPCK(hipMemcpy(st, K.d_stats, sizeof st, hipMemcpyDeviceToHost));
 	if (st[2]) return VC_EFULL;

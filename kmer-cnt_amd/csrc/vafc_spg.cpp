@@ -30,7 +30,7 @@
 #include "vafc_fastq.h"
 #include "vafc_gzip.h"
 #include "vafc_internal.h"
-#include "vafc_stage.h"
+#include "vafc_device.h"
 
 struct vc_fasta {
 	std::vector<std::string> names;
@@ -317,19 +317,23 @@ extern "C" int vc_fasta_data(const vc_fasta *fa, const uint8_t **seq, size_t *by
 
 extern "C" void vc_fasta_free(vc_fasta *fa) { delete fa; }
 
-// One synchronous upload of the sequences and their count; the caller frees
-// whatever *d_seq, *d_offs and *d_lens hold afterwards.
+// One synchronous upload of the sequences, their count and the counts back
+// (2 * n_patterns + 2 of them); the upload is freed once the count is done.
 static int count_uploaded(vc_ctx *ctx, const uint8_t *seq, size_t seq_bytes, const uint64_t *offs,
-                          const uint32_t *lens, uint64_t n_seqs, uint8_t **d_seq, uint64_t **d_offs,
-                          uint32_t **d_lens)
+                          const uint32_t *lens, uint64_t n_seqs, uint32_t *all)
 {
-	HIPCK(hipMalloc(d_seq, seq_bytes + 16));
-	HIPCK(hipMemcpy(*d_seq, seq, seq_bytes, hipMemcpyHostToDevice));
-	HIPCK(hipMalloc(d_offs, n_seqs * sizeof(uint64_t)));
-	HIPCK(hipMalloc(d_lens, n_seqs * sizeof(uint32_t)));
-	HIPCK(hipMemcpy(*d_offs, offs, n_seqs * sizeof(uint64_t), hipMemcpyHostToDevice));
-	HIPCK(hipMemcpy(*d_lens, lens, n_seqs * sizeof(uint32_t), hipMemcpyHostToDevice));
-	return vc_count_device(ctx, *d_seq, seq_bytes, *d_offs, *d_lens, n_seqs, nullptr);
+	VcDevBuf<uint8_t> d_seq;
+	VcDevBuf<uint64_t> d_offs;
+	VcDevBuf<uint32_t> d_lens;
+	if (n_seqs) {
+		HIPCK(d_seq.alloc(seq_bytes + 16));
+		HIPCK(hipMemcpy(d_seq, seq, seq_bytes, hipMemcpyHostToDevice));
+		HIPCK(d_offs.upload(offs, n_seqs));
+		HIPCK(d_lens.upload(lens, n_seqs));
+		const int rc = vc_count_device(ctx, d_seq, seq_bytes, d_offs, d_lens, n_seqs, nullptr);
+		if (rc != VC_OK) return rc;
+	}
+	return vc_finish(ctx, all, nullptr);
 }
 
 extern "C" int vc_count_candidates(int k, const uint8_t *seq, size_t seq_bytes, const uint64_t *offs,
@@ -348,15 +352,8 @@ extern "C" int vc_count_candidates(int k, const uint8_t *seq, size_t seq_bytes, 
 	int rc = vc_create(&ctx, k, keys, vals.data(), n_keys, n_patterns, device);
 	if (rc != VC_OK) return rc;
 	vc_set_nt4_decode(ctx, 1);
-	uint8_t *d_seq = nullptr;
-	uint64_t *d_offs = nullptr;
-	uint32_t *d_lens = nullptr;
-	if (n_seqs) rc = count_uploaded(ctx, seq, seq_bytes, offs, lens, n_seqs, &d_seq, &d_offs, &d_lens);
-	if (rc == VC_OK) rc = vc_finish(ctx, all.data(), nullptr);
+	rc = count_uploaded(ctx, seq, seq_bytes, offs, lens, n_seqs, all.data());
 	if (rc == VC_OK) memcpy(counts, all.data(), n_keys * sizeof(uint32_t));
-	if (d_seq) (void)hipFree(d_seq);
-	if (d_offs) (void)hipFree(d_offs);
-	if (d_lens) (void)hipFree(d_lens);
 	vc_destroy(ctx);
 	return rc;
 }

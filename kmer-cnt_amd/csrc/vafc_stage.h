@@ -1,10 +1,17 @@
-// vafc_stage.h -- how host reads reach the device, shared by the k-mer counter
-// (vafc_host.cpp) and the approximate search (vafc_ed.cpp).  Host code only.
+// vafc_stage.h -- how host batches reach the device and what a long-lived
+// device handle is made of, shared by the four handles (vc_ctx, vc_ed, vc_bam,
+// vc_vcf).  Host code only.
 //
 //   VcSlot          pinned + device buffers of one batch, released by an event
-//   VcStager        two slots filled and shipped in turn on the handle's stream
+//   VcStager        two slots filled and shipped in turn on the handle's stream;
+//                   acquire_for() gives the next slot with room for a block
 //   VcBatchWriter   reads appended into the open slot, a full slot submitted
 //   VcStreamBridge  a launch on a caller's stream, ordered with the handle's
+//   VcDevice        the core of a handle: device, stream, stager, bridge, timer;
+//                   open(), close(), stream_of(), on_stream()
+//
+// HIPCK, vc_now, the owning device buffer VcDevBuf and VcTimer are
+// vafc_device.h, which the one-shot device functions use on their own.
 #ifndef VAFC_STAGE_H
 #define VAFC_STAGE_H
 
@@ -15,29 +22,11 @@
 #include <stdlib.h>
 #include <string.h>
 #include <sys/mman.h>
-#include <time.h>
 
 #include <utility>
 
 #include "vafc.h"
-
-#define HIPCK(call)                                                                         \
-	do {                                                                                    \
-		hipError_t e_ = (call);                                                             \
-		if (e_ != hipSuccess) {                                                             \
-			fprintf(stderr, "[E::vafc] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_), \
-			        __FILE__, __LINE__);                                                    \
-			return VC_EHIP;                                                                 \
-		}                                                                                   \
-	} while (0)
-
-// Monotonic seconds.
-inline double vc_now()
-{
-	struct timespec ts;
-	clock_gettime(CLOCK_MONOTONIC, &ts);
-	return ts.tv_sec + ts.tv_nsec * 1e-9;
-}
+#include "vafc_device.h"
 
 struct VcSlot {
 	uint8_t *h_seq = nullptr;     // pinned
@@ -155,6 +144,12 @@ struct VcStager {
 		*out = &slot[cur];
 		return vc_slot_wait(slot[cur]);
 	}
+	// The same, with room for a block of (bytes, reads).
+	int acquire_for(size_t bytes, size_t reads, VcSlot **out)
+	{
+		const int rc = acquire(out);
+		return rc == VC_OK ? vc_slot_reserve(**out, bytes, reads) : rc;
+	}
 	// H2D copies of the acquired slot's first n_reads reads (bytes of sequence)
 	// and launch(slot) on stream st; the slot is released by its event.  A batch
 	// that keeps its per-record data inside the byte buffer (the BAM counter's
@@ -216,8 +211,7 @@ template <class Next> struct VcBatchWriter {
 	int open_slot()
 	{
 		if (!(h = next())) return VC_EHIP;
-		int rc = h->stage.acquire(&s);
-		if (rc == VC_OK) rc = vc_slot_reserve(*s, limit, max_reads);
+		const int rc = h->stage.acquire_for(limit, max_reads, &s);
 		if (rc != VC_OK) s = nullptr;
 		bytes = 0;
 		n = 0;
@@ -280,6 +274,64 @@ struct VcStreamBridge {
 		if (in) (void)hipEventDestroy(in);
 		if (out) (void)hipEventDestroy(out);
 		in = out = nullptr;
+	}
+};
+
+// What every long-lived handle has around its own tables: a handle derives
+// from this, declares its tables as VcDevBuf members, and its destroy
+// function is close() and delete.
+struct VcDevice {
+	int dev = 0;
+	int n_cu = 256;
+	hipStream_t st = nullptr;   // the handle's own, non-blocking
+	VcStager stage;
+	VcStreamBridge bridge;      // a launch on a caller's stream
+	VcTimer timer;
+
+	// VC_ENODEV without a device, VC_EINVAL for one that is not there; then
+	// the device is made current and the stream and every event are created.
+	// After a failure the owner still calls close().
+	int open(int device)
+	{
+		int ndev = 0;
+		if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VC_ENODEV;
+		if (device < 0 || device >= ndev) return VC_EINVAL;
+		HIPCK(hipSetDevice(device));
+		dev = device;
+		hipDeviceProp_t prop;
+		if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
+			n_cu = prop.multiProcessorCount;
+		HIPCK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+		HIPCK(timer.init());
+		return stage.init();
+	}
+	// Before the handle is deleted: waits for the stream and destroys the
+	// events.  The delete then frees the handle's VcDevBuf members while the
+	// stream still exists, and this base's destructor destroys the stream last.
+	void close()
+	{
+		(void)hipSetDevice(dev);
+		if (st) (void)hipStreamSynchronize(st);
+		stage.destroy();
+		timer.destroy();
+		bridge.destroy();
+	}
+	~VcDevice()
+	{
+		if (st) (void)hipStreamDestroy(st);
+	}
+	// NULL is HIP's null stream (ordered with the legacy default stream, which
+	// is torch's default stream), as for every HIP API; VC_STREAM_CTX is the
+	// handle's own stream.
+	hipStream_t stream_of(void *stream) const { return stream == VC_STREAM_CTX ? st : (hipStream_t)stream; }
+	// launch(stream) on a caller's stream, ordered with the handle's own.
+	template <class Launch> int on_stream(void *stream, Launch &&launch)
+	{
+		const hipStream_t s = stream_of(stream);
+		int rc = bridge.enter(st, s);
+		if (rc == VC_OK) rc = launch(s);
+		if (rc == VC_OK) rc = bridge.leave(st, s);
+		return rc;
 	}
 };
 

@@ -293,25 +293,17 @@ struct Pending {
 
 } // namespace
 
-struct vc_vcf {
-	int dev = 0;
-	int n_cu = 256;
+struct vc_vcf : VcDevice {
 	uint32_t n_rows = 0;
-	hipStream_t st = nullptr;
-	uint4 *d_table = nullptr;
+	VcDevBuf<uint4> d_table;
 	uint32_t mask = 0;
-	uint8_t *d_names = nullptr;
-	uint16_t *d_row_ra = nullptr;
-	uint4 *d_hits = nullptr;
-	size_t cap = 0;               // allocated entries of d_hits
+	VcDevBuf<uint8_t> d_names;
+	VcDevBuf<uint16_t> d_row_ra;
+	VcDevBuf<uint4> d_hits;       // max_hits entries once a scan has run
 	size_t max_hits = VCF_MAX_HITS;
-	unsigned long long *d_n_hits = nullptr;
-	uint64_t *d_consumed = nullptr;
+	VcDevBuf<unsigned long long> d_n_hits;
+	VcDevBuf<uint64_t> d_consumed;
 	size_t block_bytes = VCF_BLOCK_BYTES;
-	VcStager stage;
-	VcStreamBridge bridge;
-	hipEvent_t t0 = nullptr, t1 = nullptr;
-	bool timed = false;
 	Pending pend;
 	std::vector<vc_vcf_hit> acc;  // collected since the last vc_vcf_hits
 	bool handed = false;          // acc was returned: the next scan starts a new list
@@ -334,13 +326,7 @@ std::string host_key(const char *chr, size_t len, int32_t start)
 
 int launch(vc_vcf *c, const Pending &p)
 {
-	if (c->cap != c->max_hits) {   // hipFree waits for the kernels that still use the old list
-		if (c->d_hits) HIPCK(hipFree(c->d_hits));
-		c->d_hits = nullptr;
-		c->cap = 0;
-		HIPCK(hipMalloc((void **)&c->d_hits, (c->max_hits ? c->max_hits : 1) * sizeof(uint4)));
-		c->cap = c->max_hits;
-	}
+	if (c->d_hits.cap != c->max_hits) HIPCK(c->d_hits.grow(c->max_hits));   // max_hits >= 1
 	VcVcfArgs A;
 	A.text = p.d_text;
 	A.len = p.len;
@@ -352,18 +338,17 @@ int launch(vc_vcf *c, const Pending &p)
 	A.names = c->d_names;
 	A.row_ra = c->d_row_ra;
 	A.hits = c->d_hits;
-	A.cap = (uint32_t)(c->cap > 0xFFFFFFFFu ? 0xFFFFFFFFu : c->cap);
+	A.cap = (uint32_t)(c->d_hits.cap > 0xFFFFFFFFu ? 0xFFFFFFFFu : c->d_hits.cap);
 	A.n_hits = c->d_n_hits;
-	HIPCK(hipMemsetAsync(c->d_n_hits, 0, sizeof(unsigned long long), p.st));
-	HIPCK(hipEventRecord(c->t0, p.st));
+	HIPCK(c->d_n_hits.zero_async(p.st));
+	HIPCK(c->timer.begin(p.st));
 	hipLaunchKernelGGL(vcf_tail_kernel, dim3(1), dim3(VCF_BLOCK), 0, p.st, A);
 	HIPCK(hipGetLastError());
 	uint64_t grid = (p.len + 16 + VC_VCF_TILE_BYTES - 1) / VC_VCF_TILE_BYTES;
 	if (grid > (uint64_t)c->n_cu * 8) grid = (uint64_t)c->n_cu * 8;
 	hipLaunchKernelGGL(vcf_scan_kernel, dim3((unsigned)grid), dim3(VCF_BLOCK), 0, p.st, A);
 	HIPCK(hipGetLastError());
-	HIPCK(hipEventRecord(c->t1, p.st));
-	c->timed = true;
+	HIPCK(c->timer.end(p.st));
 	return VC_OK;
 }
 
@@ -378,7 +363,7 @@ int collect(vc_vcf *c)
 		uint64_t consumed = 0;
 		HIPCK(hipMemcpy(&n, c->d_n_hits, sizeof n, hipMemcpyDeviceToHost));
 		HIPCK(hipMemcpy(&consumed, c->d_consumed, sizeof consumed, hipMemcpyDeviceToHost));
-		if (n > c->cap) {
+		if (n > c->d_hits.cap) {
 			c->max_hits = (size_t)n;
 			const int rc = launch(c, c->pend);
 			if (rc != VC_OK) return rc;
@@ -396,38 +381,12 @@ int collect(vc_vcf *c)
 	return VC_OK;
 }
 
-int new_handle(vc_vcf **out, int device)
-{
-	*out = nullptr;
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VC_ENODEV;
-	if (device < 0 || device >= ndev) return VC_EINVAL;
-	HIPCK(hipSetDevice(device));
-	vc_vcf *c = new (std::nothrow) vc_vcf;
-	if (!c) return VC_ENOMEM;
-	c->dev = device;
-	hipDeviceProp_t prop;
-	if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-		c->n_cu = prop.multiProcessorCount;
-	*out = c;
-	return VC_OK;
-}
-
 static_assert(sizeof(vc_vcf_hit) == sizeof(uint4), "a hit is written as one 16-byte store");
 
-} // namespace
-
-extern "C" int vc_vcf_create_raw(vc_vcf **out, const char *const *chr, const int32_t *start, const char *ref,
-                                 const char *alt, size_t n, size_t table_slots, int device)
+// The rows of an open handle, on the host and as the device table.
+int vcf_fill(vc_vcf *c, const char *const *chr, const int32_t *start, const char *ref, const char *alt, size_t n,
+             size_t table_slots)
 {
-	if (!out || (n && (!chr || !start || !ref || !alt)) || n > 0x7FFFFFFFu) return VC_EINVAL;
-	*out = nullptr;
-	if (table_slots & (table_slots - 1)) return VC_EINVAL;
-	for (size_t i = 0; i < n; ++i)
-		if (!chr[i] || strlen(chr[i]) > VCF_MAX_CHR) return VC_EINVAL;
-	vc_vcf *c = nullptr;
-	int rc = new_handle(&c, device);
-	if (rc != VC_OK) return rc;
 	c->n_rows = (uint32_t)n;
 
 	// the first row of every distinct (chr, start), in file order
@@ -440,10 +399,7 @@ extern "C" int vc_vcf_create_raw(vc_vcf **out, const char *const *chr, const int
 	size_t slots = table_slots;
 	if (slots == 0)
 		for (slots = 16; slots < 2 * firsts.size(); slots <<= 1) {}
-	if (slots < firsts.size() || slots < 1 || slots > ((size_t)1 << 31)) {
-		vc_vcf_destroy(c);
-		return VC_EINVAL;
-	}
+	if (slots < firsts.size() || slots < 1 || slots > ((size_t)1 << 31)) return VC_EINVAL;
 	c->mask = (uint32_t)(slots - 1);
 	std::vector<uint4> table(slots, make_uint4(0u, 0u, VCF_EMPTY, 0u));
 	std::vector<uint8_t> names;
@@ -464,33 +420,33 @@ extern "C" int vc_vcf_create_raw(vc_vcf **out, const char *const *chr, const int
 	}
 	names.push_back(0);
 
-#define TRY(call)                                                                                  \
-	do {                                                                                           \
-		hipError_t e_ = (call);                                                                    \
-		if (e_ != hipSuccess) {                                                                    \
-			fprintf(stderr, "[E::vafc] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_),     \
-			        __FILE__, __LINE__);                                                           \
-			vc_vcf_destroy(c);                                                                     \
-			return VC_EHIP;                                                                        \
-		}                                                                                          \
-	} while (0)
-	TRY(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
-	TRY(hipMalloc((void **)&c->d_table, table.size() * sizeof(uint4)));
-	TRY(hipMemcpy(c->d_table, table.data(), table.size() * sizeof(uint4), hipMemcpyHostToDevice));
-	TRY(hipMalloc((void **)&c->d_names, names.size()));
-	TRY(hipMemcpy(c->d_names, names.data(), names.size(), hipMemcpyHostToDevice));
-	TRY(hipMalloc((void **)&c->d_row_ra, c->row_ra.size() * sizeof(uint16_t)));
-	TRY(hipMemcpy(c->d_row_ra, c->row_ra.data(), c->row_ra.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-	TRY(hipMalloc((void **)&c->d_n_hits, sizeof(unsigned long long)));
-	TRY(hipMemset(c->d_n_hits, 0, sizeof(unsigned long long)));
-	TRY(hipMalloc((void **)&c->d_consumed, sizeof(uint64_t)));
-	TRY(hipMemset(c->d_consumed, 0, sizeof(uint64_t)));
-	TRY(hipEventCreate(&c->t0));
-	TRY(hipEventCreate(&c->t1));
-#undef TRY
-	if (c->stage.init() != VC_OK) {
+	HIPCK(c->d_table.upload(table.data(), table.size()));
+	HIPCK(c->d_names.upload(names.data(), names.size()));
+	HIPCK(c->d_row_ra.upload(c->row_ra.data(), c->row_ra.size()));
+	HIPCK(c->d_n_hits.alloc(1));
+	HIPCK(c->d_n_hits.zero());
+	HIPCK(c->d_consumed.alloc(1));
+	HIPCK(c->d_consumed.zero());
+	return VC_OK;
+}
+
+} // namespace
+
+extern "C" int vc_vcf_create_raw(vc_vcf **out, const char *const *chr, const int32_t *start, const char *ref,
+                                 const char *alt, size_t n, size_t table_slots, int device)
+{
+	if (!out || (n && (!chr || !start || !ref || !alt)) || n > 0x7FFFFFFFu) return VC_EINVAL;
+	*out = nullptr;
+	if (table_slots & (table_slots - 1)) return VC_EINVAL;
+	for (size_t i = 0; i < n; ++i)
+		if (!chr[i] || strlen(chr[i]) > VCF_MAX_CHR) return VC_EINVAL;
+	vc_vcf *c = new (std::nothrow) vc_vcf;
+	if (!c) return VC_ENOMEM;
+	int rc = c->open(device);
+	if (rc == VC_OK) rc = vcf_fill(c, chr, start, ref, alt, n, table_slots);
+	if (rc != VC_OK) {
 		vc_vcf_destroy(c);
-		return VC_EHIP;
+		return rc;
 	}
 	*out = c;
 	return VC_OK;
@@ -518,18 +474,7 @@ extern "C" void vc_vcf_destroy(vc_vcf *c)
 	if (!c) return;
 	(void)hipSetDevice(c->dev);
 	if (c->pend.active && c->pend.st) (void)hipStreamSynchronize(c->pend.st);
-	if (c->st) (void)hipStreamSynchronize(c->st);
-	c->stage.destroy();
-	if (c->d_table) (void)hipFree(c->d_table);
-	if (c->d_names) (void)hipFree(c->d_names);
-	if (c->d_row_ra) (void)hipFree(c->d_row_ra);
-	if (c->d_hits) (void)hipFree(c->d_hits);
-	if (c->d_n_hits) (void)hipFree(c->d_n_hits);
-	if (c->d_consumed) (void)hipFree(c->d_consumed);
-	if (c->t0) (void)hipEventDestroy(c->t0);
-	if (c->t1) (void)hipEventDestroy(c->t1);
-	c->bridge.destroy();
-	if (c->st) (void)hipStreamDestroy(c->st);
+	c->close();
 	delete c;
 }
 
@@ -569,8 +514,7 @@ extern "C" int vc_vcf_scan_block(vc_vcf *c, const uint8_t *text, size_t len, uin
 	c->last_consumed = cons;
 	if (cons == 0) return VC_OK;
 	VcSlot *s;
-	rc = c->stage.acquire(&s);
-	if (rc == VC_OK) rc = vc_slot_reserve(*s, cons, 1);
+	rc = c->stage.acquire_for(cons, 1, &s);
 	if (rc != VC_OK) return rc;
 	memcpy(s->h_seq, text, cons);
 	return c->stage.submit(cons, 1, c->st, [&](const VcSlot &sl) {
@@ -593,18 +537,16 @@ extern "C" int vc_vcf_scan_device(vc_vcf *c, const uint8_t *d_text, size_t len, 
 	if (rc != VC_OK) return rc;
 	c->last_consumed = 0;
 	if (len == 0) return VC_OK;
-	const hipStream_t st = stream == VC_STREAM_CTX ? c->st : (hipStream_t)stream;
-	rc = c->bridge.enter(c->st, st);
-	if (rc != VC_OK) return rc;
-	c->pend.d_text = d_text;
-	c->pend.len = len;
-	c->pend.file_off = file_off;
-	c->pend.final_block = final ? 1 : 0;
-	c->pend.st = st;
-	rc = launch(c, c->pend);
-	c->pend.active = rc == VC_OK;
-	if (rc == VC_OK) rc = c->bridge.leave(c->st, st);
-	return rc;
+	return c->on_stream(stream, [&](hipStream_t st) {
+		c->pend.d_text = d_text;
+		c->pend.len = len;
+		c->pend.file_off = file_off;
+		c->pend.final_block = final ? 1 : 0;
+		c->pend.st = st;
+		const int r = launch(c, c->pend);
+		c->pend.active = r == VC_OK;
+		return r;
+	});
 }
 
 extern "C" int vc_vcf_hits(vc_vcf *c, const vc_vcf_hit **hits, size_t *n_hits, size_t *consumed)
@@ -641,10 +583,7 @@ extern "C" int vc_vcf_set_block_bytes(vc_vcf *c, size_t bytes)
 
 extern "C" int vc_vcf_kernel_ms(vc_vcf *c, float *ms)
 {
-	if (!c || !ms || !c->timed) return VC_EINVAL;
-	HIPCK(hipEventSynchronize(c->t1));
-	HIPCK(hipEventElapsedTime(ms, c->t0, c->t1));
-	return VC_OK;
+	return c ? c->timer.ms(ms) : VC_EINVAL;
 }
 
 extern "C" int vc_vcf_count_file(vc_vcf *c, const char *path, int sample_idx, int min_depth, int n_threads, uint32_t *counts,

@@ -45,6 +45,53 @@ def test_strerror_and_nodev():
         assert rc == vafc.VC_ENODEV
 
 
+def test_create_checks_arguments_before_the_device():
+    """The order of checks in every create function: a bad argument is
+    VC_EINVAL with or without a device and leaves *out NULL; valid arguments
+    without a device are VC_ENODEV."""
+    import ctypes as C
+    import torch
+    import vafc
+    L = vafc.lib()
+    db = vafc.load_patterns(os.path.join(CASES, "pat_k21.txt"))
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    offs = np.zeros(1, np.uint32)
+    chr1 = (C.c_char_p * 1)(b"chr1")
+    start = np.array([100], np.int32)
+    ref, alt = np.frombuffer(b"A", np.uint8).copy(), np.frombuffer(b"C", np.uint8).copy()
+
+    def ed(qlen):
+        h = C.c_void_p()
+        blob = np.full(max(qlen, 1), ord("A"), np.uint8)
+        return L.vc_ed_create_raw(C.byref(h), ptr(blob), ptr(offs), ptr(np.array([qlen], np.uint32)), 1, 1, 0), h
+
+    def vcf(table_slots):
+        h = C.c_void_p()
+        return L.vc_vcf_create_raw(C.byref(h), chr1, ptr(start), ptr(ref), ptr(alt), 1, table_slots, 0), h
+
+    def bam(n_refs):
+        h = C.c_void_p()
+        return L.vc_bam_create(C.byref(h), db._h, chr1, n_refs, 0), h
+
+    try:
+        for rc, h in (ed(0), ed(128), vcf(3), bam(-1)):
+            assert rc == vafc.VC_EINVAL and not h.value
+        assert L.vc_kc_create(None, 21, 1024, 0) == vafc.VC_EINVAL
+        if not torch.cuda.is_available():
+            h = C.c_void_p()
+            for rc, h in (ed(21), vcf(0), vcf(16), bam(1), (L.vc_kc_create(C.byref(h), 21, 1024, 0), h)):
+                assert rc == vafc.VC_ENODEV and not h.value
+            vaf = np.full((2, 4), 0.5)
+            depth = np.full((2, 4), 9, np.int32)
+            corr = np.zeros((2, 2))
+            ms = C.c_float()
+            rc = L.vc_corr_matrix_raw(ptr(vaf), ptr(depth), ptr(np.array([4, 4], np.int32)), 2, 4, 1, 1, ptr(corr), 0,
+                                      C.byref(ms))
+            assert rc == vafc.VC_ENODEV
+    finally:
+        db.close()
+
+
 def test_missing_pattern_file():
     import vafc
     with pytest.raises(vafc.VafcError) as e:
