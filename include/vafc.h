@@ -570,6 +570,15 @@ int vc_ed_set_counts(vc_ed *ed, const uint32_t *counts);
  * device's CU count so that a batch fills it).  Fewer ranges mean more reads
  * per block; the counts do not depend on it. */
 int vc_ed_set_max_ranges(vc_ed *ed, uint32_t max_ranges);
+/* Test hook, read-only: the kernel shape chosen at creation for the queries
+ * of one word width (0: 1..32 bytes, 32-bit words; 1: 33..64 bytes, one
+ * 64-bit word; 2: 65..127 bytes, two 64-bit words).  *n_groups: groups of 64
+ * queries, 0 when the handle has no query of that width (then *waves = 1 and
+ * *lds_masks = 1, and no kernel runs for it); *waves: groups per block, 1..4;
+ * *lds_masks: 1 when a block keeps its match masks in LDS, 0 when it reads
+ * them from HBM.  Each output may be NULL.  VC_EINVAL for a NULL handle or a
+ * width outside 0..2. */
+int vc_ed_shape(const vc_ed *ed, int width, uint32_t *n_groups, int *waves, int *lds_masks);
 /* Elapsed milliseconds of the kernels of the last count call (HIP events
  * recorded around them on the stream they ran on; synchronises on it). */
 int vc_ed_kernel_ms(vc_ed *ed, float *ms);

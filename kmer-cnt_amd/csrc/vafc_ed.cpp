@@ -313,6 +313,16 @@ extern "C" int vc_ed_set_max_ranges(vc_ed *c, uint32_t max_ranges)
 	return VC_OK;
 }
 
+extern "C" int vc_ed_shape(const vc_ed *c, int width, uint32_t *n_groups, int *waves, int *lds_masks)
+{
+	if (!c || width < 0 || width >= VC_ED_WIDTHS) return VC_EINVAL;
+	const EdWidth &E = c->width[width];
+	if (n_groups) *n_groups = E.n_groups;
+	if (waves) *waves = E.waves;
+	if (lds_masks) *lds_masks = E.lds_masks;
+	return VC_OK;
+}
+
 extern "C" int vc_ed_kernel_ms(vc_ed *c, float *ms)
 {
 	return c ? c->timer.ms(ms) : VC_EINVAL;

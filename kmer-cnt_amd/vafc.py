@@ -53,7 +53,8 @@ EXPORTS = (
     "vc_vafset_count",
     "vc_vafset_name", "vc_vafset_snps", "vc_corr_matrix", "vc_corr_matrix_raw", "vc_corr_write", "vc_corr_tree",
     "vc_ed_create", "vc_ed_create_raw", "vc_ed_destroy", "vc_ed_count_block", "vc_ed_count_device",
-    "vc_ed_finish", "vc_ed_reset", "vc_ed_set_counts", "vc_ed_set_max_ranges", "vc_ed_kernel_ms", "vc_ed_count_file",
+    "vc_ed_finish", "vc_ed_reset", "vc_ed_set_counts", "vc_ed_set_max_ranges", "vc_ed_shape", "vc_ed_kernel_ms",
+    "vc_ed_count_file",
     "vc_bam_probe", "vc_bam_kind_name", "vc_bam_read_file", "vc_bam_read_header", "vc_bam_file_refs",
     "vc_bam_file_ref_name", "vc_bam_file_records", "vc_bam_file_free", "vc_bam_index_usable", "vc_bam_build_regions",
     "vc_bam_create", "vc_bam_destroy", "vc_bam_set_regions", "vc_bam_count_block", "vc_bam_count_device",
@@ -236,6 +237,7 @@ def lib():
         "vc_ed_reset": (C.c_int, [P]),
         "vc_ed_set_counts": (C.c_int, [P, P]),
         "vc_ed_set_max_ranges": (C.c_int, [P, C.c_uint32]),
+        "vc_ed_shape": (C.c_int, [P, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "vc_ed_kernel_ms": (C.c_int, [P, C.POINTER(C.c_float)]),
         "vc_ed_count_file": (C.c_int, [P, C.c_char_p, C.c_int, C.POINTER(FileStats)]),
         "vc_bam_probe": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
@@ -1363,6 +1365,13 @@ class EdCounter:
         """At most n read ranges per query block in later count calls (0: sized
         from the device); a test hook, the counts do not depend on it."""
         _ck(lib().vc_ed_set_max_ranges(self._h, n), "vc_ed_set_max_ranges")
+
+    def shape(self, width: int):
+        """(n_groups, waves, lds_masks) of the kernel for word width 0, 1 or 2
+        (queries of 1..32, 33..64, 65..127 bytes); n_groups = 0: no such query."""
+        g, w, m = C.c_uint32(), C.c_int(), C.c_int()
+        _ck(lib().vc_ed_shape(self._h, width, C.byref(g), C.byref(w), C.byref(m)), "vc_ed_shape")
+        return g.value, w.value, bool(m.value)
 
     def kernel_ms(self) -> float:
         ms = C.c_float()

@@ -77,6 +77,9 @@ def test_create_checks_arguments_before_the_device():
         for rc, h in (ed(0), ed(128), vcf(3), bam(-1)):
             assert rc == vafc.VC_EINVAL and not h.value
         assert L.vc_kc_create(None, 21, 1024, 0) == vafc.VC_EINVAL
+        g, w, m = C.c_uint32(7), C.c_int(7), C.c_int(7)     # no handle: nothing is written
+        assert L.vc_ed_shape(None, 0, C.byref(g), C.byref(w), C.byref(m)) == vafc.VC_EINVAL
+        assert (g.value, w.value, m.value) == (7, 7, 7)
         if not torch.cuda.is_available():
             h = C.c_void_p()
             for rc, h in (ed(21), vcf(0), vcf(16), bam(1), (L.vc_kc_create(C.byref(h), 21, 1024, 0), h)):

@@ -1,7 +1,8 @@
 """ed-vaf-counter: approximate pattern search in reads.
 
-CPU: a Python statement of the contract (include/vafc.h, vc_ed_create): a
-plain DP and a numpy form over queries, checked against each other; the
+CPU: a Python statement of the contract (include/vafc.h, vc_ed_create; it
+lives in tests/ed_fixture.py): a plain DP and a numpy form over queries,
+checked against each other; the
 statement, run through Python restatements of the pattern loader
 (ed-vaf-counter.c:47-83), the kseq reader (kseq.h:192-232) and the .vaf writer
 (ed-vaf-counter.c:204-228), reproduces every golden .vaf of
@@ -20,6 +21,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, PKG
+from ed_fixture import Statement, dp_hits, pad_w, rule, scan_read  # noqa: F401  (the statement)
 
 ED = os.path.join(GOLDEN, "ed")
 CLI = os.path.join(PKG, "lib", "ed-vaf-counter")
@@ -30,97 +32,6 @@ for _case in MANIFEST.values():      # "=<case>": the same content as that case'
     for _fn, _text in _case["files"].items():
         if _text.startswith("="):
             _case["files"][_fn] = MANIFEST[_text[1:]]["files"][_fn]
-
-
-# ---------------------------------------------------------------------------
-# the statement
-# ---------------------------------------------------------------------------
-
-def pad_w(m):
-    return 64 * ((m + 63) // 64) - m
-
-
-def dp_hits(P: bytes, T: bytes, e: int) -> int:
-    """The hit count of (T, P), straight from the table."""
-    m, n = len(P), len(T)
-    if n == 0:
-        return 1
-    kp = min(m if e < 0 else e, m)
-    col = list(range(m + 1))
-    cand = []
-    for ch in T:
-        nc = [0] * (m + 1)
-        for i in range(1, m + 1):
-            nc[i] = min(col[i] + 1, nc[i - 1] + 1, col[i - 1] + (P[i - 1] != ch))
-        col = nc
-        cand.append(col[m])
-    if kp == m and n < pad_w(m):
-        cand.append(m)
-    b = min(cand)
-    return cand.count(b) if b <= kp else 0
-
-
-def scan_read(Q: np.ndarray, T: bytes):
-    """Q: uint8 [nq, m], queries of one length.  (best, cnt): the minimum of the
-    last row over the columns of T and how often it occurs, per query."""
-    nq, m = Q.shape
-    idx = np.arange(m + 1, dtype=np.int32)
-    col = np.tile(idx, (nq, 1))
-    best = np.full(nq, m + 1, np.int32)
-    cnt = np.zeros(nq, np.int64)
-    neq = {}
-    full = np.zeros((nq, m + 1), np.int32)
-    for ch in T:
-        d = neq.get(ch)
-        if d is None:
-            d = neq[ch] = (Q != ch).astype(np.int32)
-        np.minimum(col[:, 1:] + 1, col[:, :-1] + d, out=full[:, 1:])
-        # nc[i] = min(full[i], nc[i - 1] + 1): a running minimum of full[i] - i
-        col = np.minimum.accumulate(full - idx, axis=1) + idx
-        s = col[:, m]
-        lt = s < best
-        cnt = np.where(lt, 1, cnt + (s == best))
-        best = np.minimum(best, s)
-    return best, cnt
-
-
-def rule(best, cnt, n, m, e):
-    if n == 0:
-        return np.ones(len(best), np.int64)
-    kp = min(m if e < 0 else e, m)
-    c = cnt + ((best == m) if (kp == m and n < pad_w(m)) else 0)
-    return np.where(best <= kp, c, 0)
-
-
-class Statement:
-    """Per read and query length the (best, cnt) vectors, so that one scan
-    serves every -e."""
-
-    def __init__(self, queries, reads):
-        self.queries = [bytes(q) for q in queries]
-        self.by_len = {}
-        for i, q in enumerate(self.queries):
-            self.by_len.setdefault(len(q), []).append(i)
-        self.reads = [bytes(r) for r in reads]
-        self.scans = []
-        mats = {m: np.array([list(self.queries[i]) for i in ids], np.uint8).reshape(len(ids), m)
-                for m, ids in self.by_len.items()}
-        for T in self.reads:
-            self.scans.append({m: scan_read(mats[m], T) for m in mats} if T else None)
-
-    def per_read(self, e: int) -> np.ndarray:
-        """int64 [reads, queries]: the hit count of every (read, query)."""
-        out = np.zeros((len(self.reads), len(self.queries)), np.int64)
-        for r, (T, sc) in enumerate(zip(self.reads, self.scans)):
-            for m, ids in self.by_len.items():
-                out[r, ids] = 1 if sc is None else rule(sc[m][0], sc[m][1], len(T), m, e)
-        return out
-
-    def counts(self, e: int, times=None) -> np.ndarray:
-        """The counters after all reads (read r taken times[r] times)."""
-        pr = self.per_read(e)
-        out = pr.sum(axis=0) if times is None else (pr * np.asarray(times, np.int64)[:, None]).sum(axis=0)
-        return (out & 0xFFFFFFFF).astype(np.uint32)
 
 
 def test_fast_form_equals_dp():
