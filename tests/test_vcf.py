@@ -265,6 +265,59 @@ def test_probe(tmp_path):
         vafc.vcf_probe(str(tmp_path / "nope"))
 
 
+DENSE_ROWS = [(b"c", 0, b"r0", b"A", b"C"), (b"c", 4, b"r1", b"G", b"T")]
+VCF_WAVE_BYTES = 1024      # a wave of the scan kernel ranks the line starts of 1 KB of a tile
+
+
+def dense_texts():
+    """{what: (line length or None, text)}: texts of one repeated minimal
+    line, and a mixed one, that put up to 1,024 line starts into a wave's
+    1 KB.  The 15- to 17-byte lines carry an ID of 1 to 3 bytes; 16 bytes is
+    the sites-only form, where a 16-byte lane still sees at most one start."""
+    lines = {"empty": b"\n", "hit_11": b"c\t1\t.\tA\tC\t\n", "hit_14": b"c\t5\t.\tG\tT\t.\t.\n",
+             "hit_15": b"c\t1\ta\tA\tC\t.\t.\t\n", "hit_16": b"c\t1\t.\tA\tC\t.\t.\t.\n", "hit_17": b"c\t1\tabc\tA\tC\t.\t.\t\n"}
+    out = {what: (len(ln), ln * (1200 if ln == b"\n" else 400)) for what, ln in lines.items()}
+    # a hit, the row's position with other alleles, a line left to the host (five columns), an empty line
+    cycle = [b"c\t1\t.\tA\tC\t\n", b"c\t5\t.\tG\tA\t.\n", b"c\t1\t.\tA\tC\n", b"\n", b"c\t5\t.\tG\tT\t\n", b"c\t1\tid\tT\tC\t\n"]
+    assert all(8 <= len(ln) <= 12 for ln in cycle if ln != b"\n")
+    out["mixed"] = (None, b"".join(cycle[i % len(cycle)] for i in range(900)))
+    return out
+
+
+def starts_per_wave(text: bytes):
+    """Line starts in every full 1 KB of a text that lies at alignment 0."""
+    offs = np.array([off for off, _ in F.body_lines(text, 0)])
+    full = len(text) // VCF_WAVE_BYTES
+    return np.bincount(offs // VCF_WAVE_BYTES, minlength=full)[:full]
+
+
+def test_dense_texts_put_more_than_64_starts_into_a_wave():
+    """The CPU side of test_more_than_64_lines_per_wave: the scan kernel hands
+    a wave's starts to its lanes 64 at a time, and only these texts make it go
+    round twice.  16-byte lines are the edge, exactly 64 starts, 17-byte lines
+    lie on its other side."""
+    texts = dense_texts()
+    for what, (size, text) in texts.items():
+        assert 400 <= text.count(b"\n") <= 1200 and text.endswith(b"\n")
+        per_wave = starts_per_wave(text)
+        assert per_wave.size >= 1
+        if size == 16:
+            assert (per_wave == 64).all()
+        elif size == 17:
+            assert ((per_wave == 60) | (per_wave == 61)).all()
+        elif size == 1:
+            assert (per_wave == 1024).all()
+        else:
+            assert (per_wave > 64).all(), what
+        lines = F.device_lines(DENSE_ROWS, text)
+        if size == 1:
+            assert lines == [(i, -1) for i in range(1200)]
+        elif size is not None:
+            assert lines == [(i * size, 1 if size == 14 else 0) for i in range(400)]       # every line a hit
+    mixed = F.device_lines(DENSE_ROWS, texts["mixed"][1])
+    assert [r for _o, r in mixed[:4]] == [0, -1, -1, 1] and len(mixed) == 600      # two of six lines report nothing
+
+
 def test_sanitizer_run_of_the_host_parser():
     """tools/vcf_reader_asan.sh: the parser and the inflater under ASan + UBSan in
     a stand-alone program, over the goldens and their truncations."""
@@ -371,6 +424,29 @@ def test_alignment_sweep(matcher):
             hits, consumed = matcher.hits()
             assert consumed == t.rfind(b"\n", 0, len(t) - 3) + 1
             assert [(int(h["off"]), int(h["row"])) for h in hits] == F.device_lines(ROWS, t[:consumed]), (shift, pad)
+
+
+@pytest.mark.gpu
+def test_more_than_64_lines_per_wave():
+    """Minimal lines, up to 1,024 starts in a wave's 1 KB: the loop that hands
+    a wave's starts to its lanes goes round up to 16 times, and the starts are
+    ranked bit by bit.  Behind junk pads of 0..16 bytes, so that the waves'
+    borders fall on every byte of a line."""
+    import vafc
+    m = vafc.VcfMatcher(rows=[(r[0], r[1], r[3], r[4]) for r in DENSE_ROWS])
+    try:
+        for what, (_size, text) in dense_texts().items():
+            for pad in range(0, 17):
+                t = (b"x" * (pad - 1) + b"\n" if pad else b"") + text
+                got, consumed = scan(m, t)
+                want = F.device_lines(DENSE_ROWS, t)
+                assert consumed == len(t)
+                if got != want:
+                    i = next((i for i, (g, w) in enumerate(zip(got, want)) if g != w), min(len(got), len(want)))
+                    pytest.fail("%s lines behind %d bytes: %d reported, %d expected, first difference at entry %d: %r, expected %r"
+                                % (what, pad, len(got), len(want), i, got[i:i + 1], want[i:i + 1]))
+    finally:
+        m.close()
 
 
 @pytest.mark.gpu
