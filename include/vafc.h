@@ -128,12 +128,15 @@ int vc_finish(vc_ctx *ctx, uint32_t *counts, uint64_t *kmers_extracted);
 int vc_reset(vc_ctx *ctx);
 
 /* Device pointer of the uint32 counts[2*n_patterns] array (for a device-side
- * all-reduce across ranks, e.g. RCCL through torch.distributed). */
+ * all-reduce across ranks, e.g. RCCL through torch.distributed).  NULL for a
+ * histogram counter (vc_kc_create), which has no pattern counts. */
 void *vc_device_counts(vc_ctx *ctx);
 /* Count into caller-owned device buffers instead (uint32[2*n_patterns] and
  * one uint64), e.g. torch tensors that an RCCL all-reduce then sums across
- * ranks; NULL restores the ctx's own buffers.  Not zeroed by this call. */
+ * ranks; NULL restores the ctx's own buffers.  Not zeroed by this call.
+ * VC_EINVAL for a histogram counter (vc_kc_create). */
 int vc_bind_outputs(vc_ctx *ctx, void *d_counts, void *d_tally);
+/* Device pointer of the uint64 k-mer tally; NULL for a histogram counter. */
 void *vc_device_tally(vc_ctx *ctx);
 void *vc_stream(vc_ctx *ctx);
 
@@ -143,7 +146,8 @@ void *vc_stream(vc_ctx *ctx);
 int vc_set_timing(vc_ctx *ctx, int enable);
 int vc_kernel_ms(vc_ctx *ctx, float *ms);
 
-/* Table/prefilter geometry, for reports: n_keys, table slots, filter bytes. */
+/* Table/prefilter geometry, for reports: n_keys, table slots, filter bytes.
+ * VC_EINVAL for a histogram counter (vc_kc_create; its table is vc_kc_slots). */
 int vc_table_info(const vc_ctx *ctx, uint64_t *n_keys, uint64_t *slots, uint64_t *filter_bytes);
 
 /* ------------------------------------------------------------------ */
@@ -457,7 +461,8 @@ int vc_yak_bloom_select(vc_ctx *ctx, int pre, int bf_shift, int n_hash);
 
 /* Decode mode of a counter: on = seq_nt4_table at every position, the decode
  * of snp-pattern-gen (snp-pattern-gen.c:165), instead of vaf-counter's
- * position-dependent one (the default).  Applies to later count calls. */
+ * position-dependent one (the default).  Applies to later count calls.
+ * VC_EINVAL for a histogram counter (vc_kc_create). */
 int vc_set_nt4_decode(vc_ctx *ctx, int on);
 
 /* count_candidate_kmers (snp-pattern-gen.c:159-190) on the GPU: counts[i]

@@ -1,6 +1,7 @@
 // vafc_stage.h -- how host batches reach the device and what a long-lived
-// device handle is made of, shared by the four handles (vc_ctx, vc_ed, vc_bam,
-// vc_vcf).  Host code only.
+// device handle is made of, shared by the four handles (vc_ctx, in its two
+// kinds: the pattern counter and the histogram counter of vafc_ctx.h; vc_ed,
+// vc_bam, vc_vcf).  Host code only.
 //
 //   VcSlot          pinned + device buffers of one batch, released by an event
 //   VcStager        two slots filled and shipped in turn on the handle's stream;

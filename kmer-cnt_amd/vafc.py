@@ -1023,7 +1023,10 @@ class KmerHistogram(KmerMap):
     """kc-c4's kc_c4x_t (kc-c4.c:52-67) on the GPU: every canonical k-mer of the
     reads counted in one device hash table of ``slots`` 16-byte slots (0 = sized
     from free HBM).  count_block / count_device / count_file as for KmerMap;
-    ``histogram()`` is print_hist's count vector (kc-c4.c:219-231)."""
+    ``histogram()`` is print_hist's count vector (kc-c4.c:219-231).  What only
+    a pattern counter has is refused: ``bind_outputs()`` and ``table_info()``
+    raise VafcError(VC_EINVAL), as vc_set_nt4_decode returns it, and
+    vc_device_counts and vc_device_tally give NULL."""
 
     def __init__(self, k: int, slots: int = 0, device: int = 0):
         self.k, self.n_patterns, self.device = k, 0, device

@@ -1,7 +1,9 @@
-"""What the four device handles (KmerMap, EdCounter, BamCounter, VcfMatcher)
-and the one-shot correlation share around their kernels: the kernel timer, the
-device lists that grow between batches, creation and destruction, and a launch
-on a caller's stream.
+"""What the five kinds of device handle (KmerMap, KmerHistogram, EdCounter,
+BamCounter, VcfMatcher) and the one-shot correlation share around their
+kernels: the kernel timer, the device lists that grow between batches, creation
+and destruction, and a launch on a caller's stream.  KmerMap and KmerHistogram
+are the two kinds of one read counter (vc_ctx): each refuses the other's calls,
+and both go through the same file reader.
 
 The long-read list of KmerMap starts at 2^30 / 16385 + 1 entries and cannot be
 made to grow at a test-sized shape: its regrow path (ensure_long_cap in
@@ -66,6 +68,12 @@ def bam_counter(rows, names, tmp_path):
     return vafc.BamCounter(db, names)
 
 
+def kc_result(h):
+    h.finish()
+    hist, distinct, kmers = h.histogram()
+    return hist.tolist(), distinct, kmers
+
+
 class Kind:
     """create() -> handle; block(h) queues the tiny block; result(h) finishes."""
 
@@ -80,6 +88,9 @@ def kinds(tmp_path):
         "kmer": Kind(lambda: vafc.KmerMap(21, np.array([canonical(QUERY)], np.uint64), np.zeros(1, np.uint32), 1),
                      lambda h: h.count_block(*pack_reads(READS)),
                      lambda h: (h.finish()[0].tolist(), h.finish()[1])),
+        "kc": Kind(lambda: vafc.KmerHistogram(21, 1 << 16),
+                   lambda h: h.count_block(*pack_reads(READS)),
+                   kc_result),
         "ed": Kind(lambda: vafc.EdCounter(queries=[QUERY, QUERY[:12]], max_edit=1),
                    lambda h: h.count_block(*pack_reads(READS)),
                    lambda h: h.finish().tolist()),
@@ -94,6 +105,17 @@ def kinds(tmp_path):
 
 # QUERY is whole in two reads; 20 k-mers of 21 bases per 40-base read
 WANT = {"kmer": ([2, 0], 4 * 20), "ed": None, "bam": [0, 4, 0, 4], "vcf": VF.device_lines(VCF_ROWS, VCF_TEXT)}
+
+
+def kc_oracle(reads):
+    hist, distinct, kmers = oracle_reads(21, *pack_reads(reads))
+    return hist.tolist(), distinct, kmers
+
+
+@pytest.fixture(scope="module", autouse=True)
+def kc_want(built):
+    """WANT["kc"]: the oracle's histogram of READS, once the oracle is built."""
+    WANT["kc"] = kc_oracle(READS)
 
 
 def raises_einval(h):
@@ -120,13 +142,12 @@ def test_kernel_ms_needs_a_launch(kind, tmp_path):
         h.close()
 
 
-def test_kernel_ms_of_the_kmer_counter_follows_its_switch(tmp_path):
-    K = kinds(tmp_path)["kmer"]
+def timer_follows_switch(K, want):
     h = K.create()
     try:
         raises_einval(h)
         K.block(h)
-        assert K.result(h) == WANT["kmer"]
+        assert K.result(h) == want
         raises_einval(h)                       # timing is off: nothing was recorded
         h.set_timing(True)
         raises_einval(h)
@@ -142,6 +163,14 @@ def test_kernel_ms_of_the_kmer_counter_follows_its_switch(tmp_path):
         raises_einval(h)
     finally:
         h.close()
+
+
+def test_kernel_ms_of_the_kmer_counter_follows_its_switch(tmp_path):
+    timer_follows_switch(kinds(tmp_path)["kmer"], WANT["kmer"])
+
+
+def test_kernel_ms_of_the_histogram_follows_its_switch(tmp_path):
+    timer_follows_switch(kinds(tmp_path)["kc"], WANT["kc"])
 
 
 # --- 2. lists that grow between batches ------------------------------------------
@@ -200,19 +229,15 @@ def test_kc_long_list_regrows_between_batches():
         finally:
             h.close()
 
-    def oracle(reads):
-        hist, d, km = oracle_reads(21, *pack_reads(reads))
-        return hist.tolist(), d, km
-
     grown, only_second, together = run(first, second), run(second), run(first + second)
-    assert grown == together == oracle(first + second)
-    assert only_second == oracle(second)
-    assert grown[2] == only_second[2] + oracle(first)[2] and oracle(first)[2] == 8 * 80
+    assert grown == together == kc_oracle(first + second)
+    assert only_second == kc_oracle(second)
+    assert grown[2] == only_second[2] + kc_oracle(first)[2] and kc_oracle(first)[2] == 8 * 80
 
 
 # --- 3. create / destroy churn ---------------------------------------------------
 
-@pytest.mark.parametrize("kind", ["kmer", "ed", "bam", "vcf"])
+@pytest.mark.parametrize("kind", ["kmer", "kc", "ed", "bam", "vcf"])
 def test_create_destroy_rounds(kind, tmp_path):
     K = kinds(tmp_path)[kind]
     first = None
@@ -249,7 +274,84 @@ def test_correlation_rounds():
     assert first[0, 0] == first[1, 1] == first[2, 2] == 1.0
 
 
-# --- 4. VcfMatcher on a caller's stream ------------------------------------------
+# --- 4. the two kinds of read counter ---------------------------------------------
+
+def test_histogram_handle_refuses_pattern_calls(tmp_path):
+    """The calls that mean something only for one kind are VC_EINVAL (NULL, 0)
+    on the other; what every read counter has still answers, and both handles
+    count afterwards."""
+    import ctypes as C
+    import vafc
+    L, K = vafc.lib(), kinds(tmp_path)
+    n = C.c_uint64()
+    h = K["kc"].create()
+    try:
+        assert L.vc_bind_outputs(h._h, None, None) == vafc.VC_EINVAL
+        assert L.vc_table_info(h._h, C.byref(n), None, None) == vafc.VC_EINVAL
+        assert L.vc_set_nt4_decode(h._h, 1) == vafc.VC_EINVAL
+        assert L.vc_device_counts(h._h) is None and L.vc_device_tally(h._h) is None
+        assert L.vc_stream(h._h) and L.vc_shard_count(h._h) == 1
+        assert L.vc_reserve_file_ingest(h._h, 2) == vafc.VC_OK
+        K["kc"].block(h)
+        assert K["kc"].result(h) == WANT["kc"]
+    finally:
+        h.close()
+    m = K["kmer"].create()
+    try:
+        hist = np.zeros(256, np.uint64)
+        assert L.vc_kc_histogram(m._h, hist.ctypes.data, None, None) == vafc.VC_EINVAL
+        assert L.vc_kc_set_partition(m._h, 1, 0) == vafc.VC_EINVAL
+        assert L.vc_kc_track_first(m._h, 1) == vafc.VC_EINVAL
+        assert L.vc_kc_slots(m._h) == 0 and not hist.any()
+        K["kmer"].block(m)
+        assert K["kmer"].result(m) == WANT["kmer"]
+    finally:
+        m.close()
+
+
+def test_histogram_and_map_through_the_parallel_file_reader(tmp_path, monkeypatch):
+    """3,000 reads of 100 bases, with VAFC_INGEST_MIN=1 a file for the parallel
+    reader (DeviceSink) at -t 2: a KmerHistogram, then a KmerMap, then the
+    histogram again after reset(), in one process.  QUERY is planted in every
+    500th read, on either strand."""
+    import vafc
+    import oracle as O
+    rng = np.random.default_rng(74)
+    comp = bytes.maketrans(b"ACGT", b"TGCA")
+    reads = [ACGT[rng.integers(0, 4, 100)].tobytes() for _ in range(3000)]
+    for i in range(0, 3000, 500):
+        q = QUERY if i % 1000 else QUERY.translate(comp)[::-1]
+        reads[i] = reads[i][:30 + i % 7] + q + reads[i][51 + i % 7:]
+    assert all(len(r) == 100 for r in reads)
+    fq = str(tmp_path / "reads.fq")
+    with open(fq, "wb") as f:
+        f.write(b"".join(b"@r%d\n%s\n+\n%s\n" % (i, r, b"I" * 100) for i, r in enumerate(reads)))
+    monkeypatch.setenv("VAFC_INGEST_MIN", "1")
+    key = np.array([canonical(QUERY)], np.uint64)
+    orc = O.Oracle(21, keys=key, vals=np.zeros(1, np.uint32))
+    want_counts, want_kmers = orc.count_reads(*pack_reads(reads), n_patterns=1)
+    orc.close()
+    want_kc = kc_oracle(reads)
+    assert want_counts.tolist() == [6, 0] and want_kmers == want_kc[2] == 3000 * 80
+    h = vafc.KmerHistogram(21, 1 << 20)
+    m = vafc.KmerMap(21, key, np.zeros(1, np.uint32), 1)
+    try:
+        st = h.count_file(fq, 10_000_000, 2)
+        assert (st.seqs, st.bases) == (3000, 300_000)
+        assert kc_result(h) == want_kc
+        st = m.count_file(fq, 10_000_000, 2)
+        assert (st.seqs, st.bases) == (3000, 300_000)
+        counts, kmers = m.finish()
+        assert counts.tolist() == want_counts.tolist() and kmers == want_kmers
+        h.reset()
+        h.count_file(fq, 10_000_000, 2)
+        assert kc_result(h) == want_kc
+    finally:
+        h.close()
+        m.close()
+
+
+# --- 5. VcfMatcher on a caller's stream ------------------------------------------
 
 def test_vcf_scan_device_on_a_side_stream():
     """scan_device on a torch side stream straight after a scan_block on the
