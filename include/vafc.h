@@ -782,8 +782,9 @@ int vc_bam_count_file(vc_bam *b, const char *path, int n_threads, vc_file_stats 
  *    cannot be read (it does not begin with ##fileformat=VCF, a data line comes
  *    before the #CHROM line, there is no #CHROM line) gets the reference's
  *    Error: line and counts nothing; the all-zero .vaf is still written, exit 0.
- * 9. Input: plain text, gzip and BGZF (read as the multi-member gzip it is);
- *    a '\r' in front of the '\n' is dropped; a last line needs no '\n'.
+ * 9. Input: plain text, gzip and BGZF (inflated on the device, or on the host
+ *    as the multi-member gzip it is: vc_vcf_inflate_info; the result is the
+ *    same); a '\r' in front of the '\n' is dropped; a last line needs no '\n'.
  * 10. Deviations.  BCF is refused with a message naming the format.  htslib's
  *    own [W::/[E:: lines are not reproduced.  A negative sample index counts
  *    nothing.  Item 8 is reproduced where the first five columns of ANY line
@@ -897,6 +898,105 @@ int vc_vcf_kernel_ms(vc_vcf *v, float *ms);
  * bytes of text, blocks = blocks scanned. */
 int vc_vcf_count_file(vc_vcf *v, const char *path, int sample_idx, int min_depth, int n_threads, uint32_t *counts,
                       vc_file_stats *st);
+/* How the last vc_vcf_count_file got its text: BGZF members inflated on the
+ * device and members inflated on the host (the header's; all of them when the
+ * host path ran, 0 and 0 for plain text and for gzip that is not BGZF).  For
+ * BGZF input $VAFC_BGZF = host | device picks the path; unset, it is the
+ * device's.  A file the device path cannot finish (a member whose status is
+ * not 0, bytes that are no whole member before the end of the file, an ISIZE
+ * above 65,536) is counted again from its start by the host path before
+ * anything is written to counts or stderr: the result is the host path's. */
+int vc_vcf_inflate_info(const vc_vcf *v, uint64_t *device_blocks, uint64_t *host_blocks);
+
+/* ------------------------------------------------------------------ */
+/* BGZF members inflated on the device                                 */
+/* ------------------------------------------------------------------ */
+
+/* The contract:
+ *
+ * 1. A block is the raw deflate payload of one BGZF member (RFC 1951: stored,
+ *    fixed and dynamic blocks), named by a descriptor: in_len payload bytes at
+ *    in_off of the compressed buffer, isize bytes of text to out_off of the
+ *    output buffer, the trailer's crc32.  Blocks are independent: one wave
+ *    inflates one block, and no distance reaches in front of a block's text.
+ * 2. A block's status is 0 iff the stream reaches the end of its final
+ *    deflate block, the text has exactly isize bytes and its CRC-32 is crc32
+ *    (what zlib's raw inflate, its total_out and crc32() say of the same
+ *    bytes).  Payload bytes behind the final deflate block are ignored.
+ * 3. Otherwise the status is the VC_BGZF_E* code of the first defect in
+ *    stream order.  Malformed data never ends in anything else: for every
+ *    block the device reads only inside [in_off, in_off + in_len) and reads
+ *    and writes only inside [out_off, out_off + isize), and every loop of the
+ *    decoder consumes input or produces output.  Text of a block with a
+ *    non-zero status is unspecified inside that range.
+ * 4. A descriptor with isize or in_len above 65,536, or with a range that is
+ *    not inside the buffers of the call, gets VC_BGZF_EISIZE and is not
+ *    touched.  Output ranges of different blocks must not overlap. */
+typedef struct {
+	uint64_t in_off;
+	uint32_t in_len;
+	uint32_t isize;
+	uint64_t out_off;
+	uint32_t crc32;
+	uint32_t reserved;   /* 0 */
+} vc_bgzf_block;
+
+enum {
+	VC_BGZF_EBTYPE = 1,    /* block type 3 */
+	VC_BGZF_ESTORED = 2,   /* stored block: LEN is not the complement of NLEN */
+	VC_BGZF_ETOOMANY = 3,  /* more than 286 literal/length or 30 distance codes */
+	VC_BGZF_ELENS = 4,     /* a code-length set that is over-subscribed or (where that is not allowed) incomplete */
+	VC_BGZF_EREPEAT = 5,   /* a repeat with no length before it, or one that runs past the last length */
+	VC_BGZF_ENOEOB = 6,    /* no end-of-block code */
+	VC_BGZF_ESYMBOL = 7,   /* bits that are no code, literal/length symbol 286/287, distance symbol 30/31 */
+	VC_BGZF_EDIST = 8,     /* a distance that reaches in front of the block's first byte */
+	VC_BGZF_EPAST = 9,     /* more text than isize */
+	VC_BGZF_ESHORT = 10,   /* the final deflate block ended with less text than isize */
+	VC_BGZF_EINPUT = 11,   /* the payload ended before the final deflate block did */
+	VC_BGZF_ECRC = 12,     /* the text's CRC-32 is not crc32 */
+	VC_BGZF_EISIZE = 13    /* item 4 */
+};
+
+/* Host only.  The whole BGZF members at the front of raw[0..len), as
+ * descriptors: in_off from raw[0], out_off running from 0.  *n receives their
+ * number (at most cap), *consumed the bytes they take.  Returns why the walk
+ * stopped: VC_OK, all len bytes are whole members; VC_BGZF_MORE, the bytes at
+ * *consumed can be the front of a member that the end of raw cuts off and
+ * final == 0 (call again with more); VC_BGZF_NOT_MEMBER, they are not a BGZF
+ * member (another gzip member, other bytes, or a cut member with final != 0);
+ * VC_BGZF_TOO_LONG, a member with ISIZE above 65,536; VC_BGZF_FULL, cap
+ * descriptors are written and more members follow. */
+#define VC_BGZF_MORE 1
+#define VC_BGZF_NOT_MEMBER 2
+#define VC_BGZF_TOO_LONG 3
+#define VC_BGZF_FULL 4
+int vc_bgzf_index(const uint8_t *raw, size_t len, int final, vc_bgzf_block *blocks, size_t cap, size_t *n,
+                  size_t *consumed);
+
+typedef struct vc_bgzf vc_bgzf;
+int vc_bgzf_create(vc_bgzf **out, int device);
+void vc_bgzf_destroy(vc_bgzf *z);
+/* Inflate n blocks of host bytes raw[0..raw_len) into text[0..text_cap):
+ * staged through pinned memory, inflated on the handle's stream, the text
+ * copied back; text is complete on return, raw reusable.  The blocks' status
+ * comes with vc_bgzf_finish. */
+int vc_bgzf_inflate_block(vc_bgzf *z, const uint8_t *raw, size_t raw_len, const vc_bgzf_block *blocks, size_t n,
+                          uint8_t *text, size_t text_cap);
+/* The same for HBM-resident compressed bytes, descriptors and output (any
+ * alignment) on `stream`, with vc_count_device's ordering contract; the
+ * buffers must stay valid until vc_bgzf_finish or until `stream` has passed
+ * the call.  A later call replaces the status of an earlier one. */
+int vc_bgzf_inflate_device(vc_bgzf *z, const uint8_t *d_raw, size_t raw_len, const vc_bgzf_block *d_blocks, size_t n,
+                           uint8_t *d_text, size_t text_cap, void *stream);
+/* Wait for the last inflate call: status[i] (up to cap of them; may be NULL)
+ * of its blocks, *n_blocks their number, *ok_blocks the number of leading
+ * blocks whose status is 0 (the text of blocks [0, ok_blocks) is whole). */
+int vc_bgzf_finish(vc_bgzf *z, uint32_t *status, size_t cap, size_t *n_blocks, size_t *ok_blocks);
+/* Elapsed milliseconds of the kernel of the last inflate call. */
+int vc_bgzf_kernel_ms(vc_bgzf *z, float *ms);
+/* The handle's own stream (a hipStream_t), what VC_STREAM_CTX stands for. */
+void *vc_bgzf_stream(vc_bgzf *z);
+const char *vc_bgzf_status_name(uint32_t status);
 
 /* ------------------------------------------------------------------ */
 /* Synthetic workload (bench / tests): the generator of vafc_synth.py,  */

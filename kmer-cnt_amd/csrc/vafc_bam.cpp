@@ -8,6 +8,7 @@
 // worker threads inflate them side by side (raw inflate, CRC-32 and ISIZE
 // checked per block).  The next group is loaded while this one is parsed.
 #include "vafc_bam.h"
+#include "vafc_bgzf.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -22,21 +23,11 @@
 namespace {
 
 const size_t BGZF_GROUP_BLOCKS = 256;   // blocks inflated side by side (up to 16 MB of text)
-const uint32_t BGZF_MAX_TEXT = 65536;   // of one block
+const uint32_t BGZF_MAX_TEXT = VC_BGZF_MAX_TEXT;   // of one block
 
-inline uint32_t le16(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
-inline uint32_t le32(const uint8_t *p) { return le16(p) | le16(p + 2) << 16; }
-
-// The BSIZE of a member from its extra field (xlen bytes), or -1.
-int bgzf_bsize(const uint8_t *extra, size_t xlen)
-{
-	for (size_t i = 0; i + 4 <= xlen;) {
-		const size_t slen = le16(extra + i + 2);
-		if (extra[i] == 'B' && extra[i + 1] == 'C' && slen == 2 && i + 6 <= xlen) return (int)le16(extra + i + 4);
-		i += 4 + slen;
-	}
-	return -1;
-}
+// (the member walk is vafc_bgzf.h's, shared with the device inflater)
+inline uint32_t le16(const uint8_t *p) { return vc_le16(p); }
+inline uint32_t le32(const uint8_t *p) { return vc_le32(p); }
 
 // Inflate one whole member (size bytes, its extra field xlen long) into out,
 // which has room for its ISIZE; false unless it inflates to exactly ISIZE
@@ -67,14 +58,14 @@ int bgzf_read_member(FILE *fp, std::vector<uint8_t> &raw)
 	uint8_t h[12];
 	const size_t got = fread(h, 1, 12, fp);
 	if (got == 0) return 0;
-	if (got != 12 || h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) return -1;
-	const size_t xlen = le16(h + 10), at = raw.size();
+	if (got != 12 || !vc_bgzf_head_ok(h)) return -1;
+	const size_t xlen = vc_bgzf_xlen(h), at = raw.size();
 	raw.insert(raw.end(), h, h + 12);
 	raw.resize(at + 12 + xlen);
 	if (xlen && fread(raw.data() + at + 12, 1, xlen, fp) != xlen) return raw.resize(at), -1;
-	const int bsize = bgzf_bsize(raw.data() + at + 12, xlen);
-	if (bsize < 0 || (size_t)bsize + 1 < 12 + xlen + 8) return raw.resize(at), -1;
-	const size_t rest = (size_t)bsize + 1 - 12 - xlen;
+	const size_t size = vc_bgzf_member_size(raw.data() + at + 12, xlen);
+	if (size == 0) return raw.resize(at), -1;
+	const size_t rest = size - 12 - xlen;
 	raw.resize(at + 12 + xlen + rest);
 	if (fread(raw.data() + at + 12 + xlen, 1, rest, fp) != rest) return raw.resize(at), -1;
 	return 1;

@@ -63,7 +63,9 @@ EXPORTS = (
     "vc_vcf_probe", "vc_vcf_kind_name", "vc_vcf_header_parse", "vc_vcf_header_samples", "vc_vcf_header_type",
     "vc_vcf_header_free", "vc_vcf_eval_line", "vc_vcf_create", "vc_vcf_create_raw", "vc_vcf_destroy",
     "vc_vcf_scan_block", "vc_vcf_scan_device", "vc_vcf_hits", "vc_vcf_set_max_hits", "vc_vcf_set_block_bytes",
-    "vc_vcf_kernel_ms", "vc_vcf_count_file",
+    "vc_vcf_kernel_ms", "vc_vcf_count_file", "vc_vcf_inflate_info",
+    "vc_bgzf_index", "vc_bgzf_create", "vc_bgzf_destroy", "vc_bgzf_inflate_block", "vc_bgzf_inflate_device",
+    "vc_bgzf_finish", "vc_bgzf_kernel_ms", "vc_bgzf_stream", "vc_bgzf_status_name",
     "vc_synth_reads",
     "vc_debug_decode", "vc_strerror", "vc_version", "vc_build_id",
 )
@@ -278,6 +280,16 @@ def lib():
         "vc_vcf_set_block_bytes": (C.c_int, [P, C.c_size_t]),
         "vc_vcf_kernel_ms": (C.c_int, [P, C.POINTER(C.c_float)]),
         "vc_vcf_count_file": (C.c_int, [P, C.c_char_p, C.c_int, C.c_int, C.c_int, P, C.POINTER(FileStats)]),
+        "vc_vcf_inflate_info": (C.c_int, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "vc_bgzf_index": (C.c_int, [P, C.c_size_t, C.c_int, P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+        "vc_bgzf_create": (C.c_int, [C.POINTER(P), C.c_int]),
+        "vc_bgzf_destroy": (None, [P]),
+        "vc_bgzf_inflate_block": (C.c_int, [P, P, C.c_size_t, P, C.c_size_t, P, C.c_size_t]),
+        "vc_bgzf_inflate_device": (C.c_int, [P, P, C.c_size_t, P, C.c_size_t, P, C.c_size_t, P]),
+        "vc_bgzf_finish": (C.c_int, [P, P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+        "vc_bgzf_kernel_ms": (C.c_int, [P, C.POINTER(C.c_float)]),
+        "vc_bgzf_stream": (P, [P]),
+        "vc_bgzf_status_name": (C.c_char_p, [C.c_uint32]),
         "vc_synth_reads": (C.c_int, [P, P, P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64,
                                      C.c_double, P, P, C.c_uint32, P]),
         "vc_debug_decode": (C.c_int, [P, C.c_size_t, P, P, C.c_uint64, P, P]),
@@ -1753,6 +1765,12 @@ class VcfMatcher:
         _ck(lib().vc_vcf_kernel_ms(self._h, C.byref(ms)), "vc_vcf_kernel_ms")
         return ms.value
 
+    def inflate_info(self):
+        """(BGZF members the device inflated, members the host inflated) for the last count_file."""
+        d, h = C.c_uint64(), C.c_uint64()
+        _ck(lib().vc_vcf_inflate_info(self._h, C.byref(d), C.byref(h)), "vc_vcf_inflate_info")
+        return d.value, h.value
+
     def count_file(self, fn: str, sample_idx: int = 0, min_depth: int = 1, n_thread: int = 4, counts=None):
         """process_vcf with its stderr lines: (counts uint32[2 * n_rows], FileStats).
         FileNotFoundError if the file cannot be opened, VafcError(VC_EINVAL) if
@@ -1770,6 +1788,84 @@ class VcfMatcher:
     def close(self):
         if getattr(self, "_h", None):
             lib().vc_vcf_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# --------------------------------------------------------------------------
+# BGZF members inflated on the GPU
+# --------------------------------------------------------------------------
+
+BGZF_BLOCK = np.dtype([("in_off", "<u8"), ("in_len", "<u4"), ("isize", "<u4"), ("out_off", "<u8"), ("crc32", "<u4"),
+                       ("reserved", "<u4")])     # vc_bgzf_block
+BGZF_WHY = ("ok", "more", "not_member", "too_long", "full")   # vc_bgzf_index's return value
+
+
+def bgzf_index(raw: bytes, final: bool = True, cap: int = None):
+    """The whole BGZF members at the front of raw: (descriptors as a BGZF_BLOCK
+    array with running out_off, bytes they take, why the walk stopped: one of
+    BGZF_WHY)."""
+    cap = len(raw) // 26 + 1 if cap is None else cap
+    blocks = np.zeros(max(cap, 1), dtype=BGZF_BLOCK)
+    n, consumed = C.c_size_t(), C.c_size_t()
+    buf = C.create_string_buffer(bytes(raw), len(raw))
+    rc = lib().vc_bgzf_index(C.cast(buf, P), len(raw), int(final), _ptr(blocks), cap, C.byref(n), C.byref(consumed))
+    if rc < 0:
+        _ck(rc, "vc_bgzf_index")
+    return blocks[:n.value].copy(), consumed.value, BGZF_WHY[rc]
+
+
+class BgzfInflater:
+    """BGZF members inflated on the GPU, one wave per member (vc_bgzf_*)."""
+
+    def __init__(self, device: int = 0):
+        h = P()
+        _ck(lib().vc_bgzf_create(C.byref(h), device), "vc_bgzf_create")
+        self._h = h
+
+    def inflate(self, raw: bytes, blocks: np.ndarray = None, text_cap: int = None, fill: int = 0) -> bytes:
+        """The text of the members of raw (blocks: their descriptors, default
+        bgzf_index's), text_cap bytes of it (default: up to the last block's
+        end; bytes no block writes keep the value `fill`).  status() tells
+        which blocks are whole."""
+        if blocks is None:
+            blocks = bgzf_index(raw)[0]
+        blocks = np.ascontiguousarray(blocks, dtype=BGZF_BLOCK)
+        if text_cap is None:
+            text_cap = int((blocks["out_off"] + blocks["isize"]).max()) if len(blocks) else 0
+        text = np.full(max(text_cap, 1), fill, dtype=np.uint8)
+        buf = np.frombuffer(bytes(raw), dtype=np.uint8) if len(raw) else np.zeros(1, np.uint8)
+        _ck(lib().vc_bgzf_inflate_block(self._h, _ptr(buf), len(raw), _ptr(blocks) if len(blocks) else None, len(blocks),
+                                        _ptr(text), text_cap), "vc_bgzf_inflate_block")
+        return text[:text_cap].tobytes()
+
+    def inflate_device(self, raw_ptr: int, raw_len: int, blocks_ptr: int, n_blocks: int, text_ptr: int, text_cap: int,
+                       stream: int = 0) -> None:
+        """HBM-resident compressed bytes, descriptors and output on `stream` (as KmerMap.count_device)."""
+        _ck(lib().vc_bgzf_inflate_device(self._h, P(raw_ptr), raw_len, P(blocks_ptr), n_blocks, P(text_ptr), text_cap,
+                                         P(stream) if stream else None), "vc_bgzf_inflate_device")
+
+    def status(self):
+        """(status of every block of the last call as uint32, the number of leading blocks that are ok)."""
+        n, ok = C.c_size_t(), C.c_size_t()
+        _ck(lib().vc_bgzf_finish(self._h, None, 0, C.byref(n), C.byref(ok)), "vc_bgzf_finish")
+        st = np.zeros(max(n.value, 1), dtype=np.uint32)
+        _ck(lib().vc_bgzf_finish(self._h, _ptr(st), n.value, C.byref(n), C.byref(ok)), "vc_bgzf_finish")
+        return st[:n.value], ok.value
+
+    def kernel_ms(self) -> float:
+        ms = C.c_float()
+        _ck(lib().vc_bgzf_kernel_ms(self._h, C.byref(ms)), "vc_bgzf_kernel_ms")
+        return ms.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().vc_bgzf_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""End to end: vcf-vaf-counter on one BGZF-compressed VCF, the parent commit's
+binary against this tree's, alternating in one call.
+
+The file: a VCF header, then a seeded chunk of 100-sample lines
+(tests/vcf_fixture.synth_vcf against the GRCh38 panel) as BGZF members of
+65,280 bytes of text at level 6, the chunk's members repeated until the file
+holds at least --bytes of text, then the EOF member.  --parent is the parent
+commit's vcf-vaf-counter (built from a checkout of it into a directory of its
+own), --branch this tree's (default lib/vcf-vaf-counter, run with
+VAFC_BGZF=device; --branch-host adds a leg with VAFC_BGZF=host).  The runs
+alternate parent, branch, parent, ... --runs times each after one untimed run
+of each; the wall clock of each process is taken with a host clock, and the
+.vaf files must be identical.  One JSON object: the seconds of every run, the
+medians, the parent's own spread (max - min) and the verdict of the rule that
+chooses the default: the device path is the default for BGZF input only if the
+branch's median is not above the parent's by more than that spread.
+
+    python tools/vcf_bgzf_e2e.py --parent DIR/vcf-vaf-counter [--bytes 2147483648] [--out profiles/vcf_bgzf_e2e.json]
+"""
+import argparse
+import hashlib
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+import zlib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "kmer-cnt_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+PAYLOAD = 65280
+
+
+def member(piece):
+    c = zlib.compressobj(6, zlib.DEFLATED, -15)
+    comp = c.compress(piece) + c.flush()
+    total = 18 + len(comp) + 8
+    return (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + (total - 1).to_bytes(2, "little") + comp +
+            zlib.crc32(piece).to_bytes(4, "little") + len(piece).to_bytes(4, "little"))
+
+
+def make_file(path, n_bytes, rows, chunk_bytes=32 << 20):
+    import vcf_fixture as F
+    chunk = F.synth_vcf(rows, chunk_bytes // 1260 + 1, 100, seed=3, hit_rate=0.004, header_too=False)
+    head = F.header(samples=["S%d" % i for i in range(100)]).encode()
+    # the chunk begins at a member border, so that its members can be repeated as they are
+    body = b"".join(member(chunk[i:i + PAYLOAD]) for i in range(0, len(chunk), PAYLOAD))
+    reps = max(1, -(-n_bytes // len(chunk)))
+    with open(path, "wb") as f:
+        f.write(member(head))
+        for _ in range(reps):
+            f.write(body)
+        f.write(member(b""))
+    return len(head) + reps * len(chunk), os.path.getsize(path)
+
+
+def run(binary, env_bgzf, patterns, vcf, out):
+    env = dict(os.environ)
+    env.pop("VAFC_BGZF", None)
+    if env_bgzf:
+        env["VAFC_BGZF"] = env_bgzf
+    t0 = time.perf_counter()
+    p = subprocess.run([binary, "-p", patterns, "-v", vcf, "-o", out], capture_output=True, text=True, env=env, timeout=600)
+    dt = time.perf_counter() - t0
+    if p.returncode != 0:
+        sys.exit("vcf_bgzf_e2e: %s failed: %s" % (binary, p.stderr[-1000:]))
+    with open(out, "rb") as f:
+        return dt, hashlib.sha256(f.read()).hexdigest()
+
+
+def median(v):
+    v = sorted(v)
+    return v[len(v) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent", required=True)
+    ap.add_argument("--branch", default=os.path.join(ROOT, "kmer-cnt_amd", "lib", "vcf-vaf-counter"))
+    ap.add_argument("--branch-host", action="store_true")
+    ap.add_argument("--bytes", type=int, default=2 << 30)
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    import vcf_bench
+    rows = vcf_bench.panel_rows("grch38")
+    with tempfile.TemporaryDirectory(dir=os.environ.get("TMPDIR")) as tmp:
+        pat, vcf = os.path.join(tmp, "p.txt"), os.path.join(tmp, "s.vcf.gz")
+        vcf_bench.write_patterns(rows, pat)
+        text_bytes, file_bytes = make_file(vcf, a.bytes, rows)
+        legs = [("parent", a.parent, None), ("branch", a.branch, "device")]
+        if a.branch_host:
+            legs.append(("branch_host", a.branch, "host"))
+        secs = {name: [] for name, _b, _e in legs}
+        shas = set()
+        for i in range(a.runs + 1):
+            for name, binary, env in legs:
+                dt, sha = run(binary, env, pat, vcf, os.path.join(tmp, name + ".vaf"))
+                shas.add(sha)
+                if i:
+                    secs[name].append(round(dt, 4))
+        if len(shas) != 1:
+            sys.exit("vcf_bgzf_e2e: the .vaf files differ")
+    spread = max(secs["parent"]) - min(secs["parent"])
+    res = dict(tool="vcf_bgzf_e2e", text_bytes=text_bytes, file_bytes=file_bytes, samples=100, runs=a.runs, seconds=secs,
+               median={k: median(v) for k, v in secs.items()}, parent_spread=round(spread, 4), vaf_sha256=shas.pop(),
+               vaf_identical=True)
+    res["device_default"] = res["median"]["branch"] <= res["median"]["parent"] + spread
+    res["text_GBps"] = {k: round(text_bytes / v / 1e9, 3) for k, v in res["median"].items()}
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
