@@ -6,72 +6,20 @@
 // a BC extra field, so the parallel cut is given: a group of blocks is read,
 // its members' ISIZE words give every block's place in the group's text, and
 // worker threads inflate them side by side (raw inflate, CRC-32 and ISIZE
-// checked per block).  The next group is loaded while this one is parsed.
+// checked per block, vafc_bgzf_io.h).  The next group is loaded while this one is parsed.
 #include "vafc_bam.h"
-#include "vafc_bgzf.h"
+#include "vafc_bgzf_io.h"
 
 #include <stdlib.h>
 #include <string.h>
 #include <sys/stat.h>
-#include <zlib.h>
 
 #include <algorithm>
 #include <atomic>
 #include <new>
 #include <thread>
 
-namespace {
-
-const size_t BGZF_GROUP_BLOCKS = 256;   // blocks inflated side by side (up to 16 MB of text)
-const uint32_t BGZF_MAX_TEXT = VC_BGZF_MAX_TEXT;   // of one block
-
-// (the member walk is vafc_bgzf.h's, shared with the device inflater)
-inline uint32_t le16(const uint8_t *p) { return vc_le16(p); }
-inline uint32_t le32(const uint8_t *p) { return vc_le32(p); }
-
-// Inflate one whole member (size bytes, its extra field xlen long) into out,
-// which has room for its ISIZE; false unless it inflates to exactly ISIZE
-// bytes with the CRC-32 of its trailer.
-bool bgzf_inflate(const uint8_t *blk, size_t size, uint8_t *out)
-{
-	const size_t xlen = le16(blk + 10), head = 12 + xlen;
-	if (size < head + 8) return false;
-	const uint32_t want_crc = le32(blk + size - 8), isize = le32(blk + size - 4);
-	z_stream zs;
-	memset(&zs, 0, sizeof zs);
-	if (inflateInit2(&zs, -15) != Z_OK) return false;
-	uint8_t dummy;
-	zs.next_in = const_cast<uint8_t *>(blk + head);
-	zs.avail_in = (uInt)(size - head - 8);
-	zs.next_out = isize ? out : &dummy;
-	zs.avail_out = isize ? isize : 1;   // text longer than ISIZE ends in Z_BUF_ERROR or a wrong total_out
-	const int rc = inflate(&zs, Z_FINISH);
-	const bool ok = rc == Z_STREAM_END && zs.total_out == isize;
-	inflateEnd(&zs);
-	return ok && (uint32_t)crc32(crc32(0L, Z_NULL, 0), out, isize) == want_crc;
-}
-
-// Read one member at the file position into `raw` (appended); 1 = read, 0 =
-// clean end of file, -1 = truncated or not a BGZF member.
-int bgzf_read_member(FILE *fp, std::vector<uint8_t> &raw)
-{
-	uint8_t h[12];
-	const size_t got = fread(h, 1, 12, fp);
-	if (got == 0) return 0;
-	if (got != 12 || !vc_bgzf_head_ok(h)) return -1;
-	const size_t xlen = vc_bgzf_xlen(h), at = raw.size();
-	raw.insert(raw.end(), h, h + 12);
-	raw.resize(at + 12 + xlen);
-	if (xlen && fread(raw.data() + at + 12, 1, xlen, fp) != xlen) return raw.resize(at), -1;
-	const size_t size = vc_bgzf_member_size(raw.data() + at + 12, xlen);
-	if (size == 0) return raw.resize(at), -1;
-	const size_t rest = size - 12 - xlen;
-	raw.resize(at + 12 + xlen + rest);
-	if (fread(raw.data() + at + 12 + xlen, 1, rest, fp) != rest) return raw.resize(at), -1;
-	return 1;
-}
-
-} // namespace
+static const size_t BGZF_GROUP_BLOCKS = 256;   // blocks inflated side by side (up to 16 MB of text)
 
 bool VcBgzf::open(const char *path, int n_threads)
 {
@@ -96,33 +44,31 @@ void VcBgzf::close()
 
 void VcBgzf::load(VcBgzfGroup *g)
 {
-	g->raw.clear();
 	g->boff.assign(1, 0);
 	g->toff.assign(1, 0);
 	g->text_len = 0;
 	g->last = false;
-	while (g->boff.size() <= BGZF_GROUP_BLOCKS) {
-		const int rc = bgzf_read_member(fp_, g->raw);
-		if (rc <= 0) {
+	std::vector<VcBgzfMember> mem;
+	while (mem.size() < BGZF_GROUP_BLOCKS) {
+		// raw only grows: the blocks end at boff[n], not at its size
+		const size_t at = g->boff.back();
+		if (g->raw.size() < at + VC_BGZF_MAX_MEMBER) g->raw.resize(at + VC_BGZF_MAX_MEMBER);
+		VcBgzfMember m;
+		if (vc_bgzf_read_member(fp_, g->raw.data() + at, &m) <= 0) {   // (an ISIZE no BGZF block can hold among them)
 			g->last = true;
 			break;
 		}
-		const uint32_t isize = le32(g->raw.data() + g->raw.size() - 4);
-		if (isize > BGZF_MAX_TEXT) {   // no BGZF block holds more: it cannot inflate
-			g->raw.resize(g->boff.back());
-			g->last = true;
-			break;
-		}
-		g->boff.push_back((uint32_t)g->raw.size());
-		g->toff.push_back(g->toff.back() + isize);
+		mem.push_back(m);
+		g->boff.push_back((uint32_t)(at + m.size));
+		g->toff.push_back(g->toff.back() + m.isize);
 	}
-	const size_t n = g->boff.size() - 1;
+	const size_t n = mem.size();
 	if (g->text.size() < g->toff[n] + 1) g->text.resize(g->toff[n] + 1);
 	std::vector<uint8_t> ok(n, 0);
 	std::atomic<size_t> next(0);
 	auto work = [&]() {
 		for (size_t i; (i = next.fetch_add(1)) < n;)
-			ok[i] = bgzf_inflate(g->raw.data() + g->boff[i], g->boff[i + 1] - g->boff[i], g->text.data() + g->toff[i]);
+			ok[i] = vc_bgzf_inflate_member(g->raw.data() + g->boff[i], mem[i], g->text.data() + g->toff[i]);
 	};
 	const size_t nt = std::min<size_t>((size_t)threads_, n);
 	std::vector<std::thread> pool;
@@ -197,16 +143,18 @@ extern "C" const char *vc_bam_kind_name(int kind)
 
 namespace {
 
-// The text of the first BGZF member of a file (empty: none that inflates).
-std::vector<uint8_t> first_member_text(FILE *fp)
+// The text of the first BGZF member of a file (empty: none that inflates);
+// *read: whether it is one (vc_bgzf_read_member).
+std::vector<uint8_t> first_member_text(FILE *fp, int *read = nullptr)
 {
-	std::vector<uint8_t> raw, text;
-	if (bgzf_read_member(fp, raw) != 1) return text;
-	const uint32_t isize = le32(raw.data() + raw.size() - 4);
-	if (isize > BGZF_MAX_TEXT) return text;
-	text.resize(isize + 1);
-	if (!bgzf_inflate(raw.data(), raw.size(), text.data())) return std::vector<uint8_t>();
-	text.resize(isize);
+	std::vector<uint8_t> raw(VC_BGZF_MAX_MEMBER), text;
+	VcBgzfMember m;
+	const int r = vc_bgzf_read_member(fp, raw.data(), &m);
+	if (read) *read = r;
+	if (r != 1) return text;
+	text.resize(m.isize + 1);
+	if (!vc_bgzf_inflate_member(raw.data(), m, text.data())) return std::vector<uint8_t>();
+	text.resize(m.isize);
 	return text;
 }
 
@@ -223,16 +171,12 @@ extern "C" int vc_bam_probe(const char *path, int *kind)
 	else if (got >= 4 && memcmp(h, "BAM\1", 4) == 0) *kind = VC_BAM_RAW;
 	else if (got >= 2 && h[0] == 31 && h[1] == 139) {
 		rewind(fp);
-		std::vector<uint8_t> raw;
-		if (bgzf_read_member(fp, raw) < 0) {
-			// a BGZF header that is cut short still names BGZF; anything else is plain gzip
-			*kind = got == 12 && h[2] == 8 && (h[3] & 4) && le16(h + 10) >= 6 ? VC_BAM_BGZF : VC_BAM_GZIP;
-		} else {
-			rewind(fp);
-			const std::vector<uint8_t> text = first_member_text(fp);
-			// a first block that does not inflate is a header that cannot be read
-			*kind = text.size() >= 4 && memcmp(text.data(), "BAM\1", 4) != 0 ? VC_BAM_BGZF_OTHER : VC_BAM_BGZF;
-		}
+		int read = 0;
+		const std::vector<uint8_t> text = first_member_text(fp, &read);
+		// a BGZF header that is cut short still names BGZF; anything else is plain gzip
+		if (read < 0) *kind = got == 12 && h[2] == 8 && (h[3] & 4) && vc_le16(h + 10) >= 6 ? VC_BAM_BGZF : VC_BAM_GZIP;
+		// a first block that does not inflate is a header that cannot be read
+		else *kind = text.size() >= 4 && memcmp(text.data(), "BAM\1", 4) != 0 ? VC_BAM_BGZF_OTHER : VC_BAM_BGZF;
 	} else {
 		*kind = VC_BAM_SAM;
 	}
@@ -256,13 +200,13 @@ int VcBamReader::open(const char *path, int n_threads)
 	ended_ = true;
 	const uint8_t *p = z_.take(8);
 	if (!p || memcmp(p, "BAM\1", 4) != 0) return VC_EINVAL;
-	const int32_t l_text = (int32_t)le32(p + 4);
+	const int32_t l_text = (int32_t)vc_le32(p + 4);
 	if (l_text < 0 || !z_.take((size_t)l_text) || !(p = z_.take(4))) return VC_EINVAL;
-	const int32_t n_ref = (int32_t)le32(p);
+	const int32_t n_ref = (int32_t)vc_le32(p);
 	if (n_ref < 0) return VC_EINVAL;
 	for (int32_t i = 0; i < n_ref; ++i) {
 		if (!(p = z_.take(4))) return VC_EINVAL;
-		const int32_t l_name = (int32_t)le32(p);
+		const int32_t l_name = (int32_t)vc_le32(p);
 		if (l_name < 1 || !(p = z_.take((size_t)l_name))) return VC_EINVAL;
 		refs_.emplace_back((const char *)p, strnlen((const char *)p, (size_t)l_name));
 		if (!z_.take(4)) return VC_EINVAL;
@@ -305,7 +249,7 @@ int find_cg(const uint8_t *a, const uint8_t *e, const uint8_t **words, uint32_t 
 			case 'i': case 'I': case 'f': el = 4; break;
 			default: return -1;
 			}
-			const uint64_t cnt = le32(a + 1);
+			const uint64_t cnt = vc_le32(a + 1);
 			if (cnt * el > (uint64_t)(e - a - 5)) return -1;
 			if (cg) {
 				if (a[0] != 'I' && a[0] != 'i') return 0;
@@ -344,7 +288,7 @@ bool VcBamReader::next_batch(std::vector<vc_bam_rec> &recs, std::vector<uint8_t>
 			ended_ = true;
 			break;
 		}
-		const int32_t bl = (int32_t)le32(p);
+		const int32_t bl = (int32_t)vc_le32(p);
 		if (bl < 32) {
 			soft_fail();
 			continue;
@@ -354,12 +298,12 @@ bool VcBamReader::next_batch(std::vector<vc_bam_rec> &recs, std::vector<uint8_t>
 			break;
 		}
 		vc_bam_rec r;
-		r.tid = (int32_t)le32(p);
-		r.pos = (int32_t)le32(p + 4);
+		r.tid = (int32_t)vc_le32(p);
+		r.pos = (int32_t)vc_le32(p + 4);
 		const uint32_t l_qname = p[8];
-		r.n_cigar = le16(p + 12);
-		r.flag = le16(p + 14);
-		r.l_seq = le32(p + 16);
+		r.n_cigar = vc_le16(p + 12);
+		r.flag = vc_le16(p + 14);
+		r.l_seq = vc_le32(p + 16);
 		r.reserved = 0;
 		const uint64_t seq_bytes = ((uint64_t)r.l_seq + 1) >> 1;
 		if ((int32_t)r.l_seq < 0 || l_qname < 1 ||
@@ -374,7 +318,7 @@ bool VcBamReader::next_batch(std::vector<vc_bam_rec> &recs, std::vector<uint8_t>
 		}
 		const uint8_t *cigar = p + l_qname, *seq = cigar + 4 * (size_t)r.n_cigar;
 		// the long-CIGAR convention (sam.c bam_tag2cigar): <l_seq>S<N>N plus CG:B,I
-		if (r.n_cigar > 0 && le32(cigar) == (r.l_seq << 4 | 4u) && r.tid >= 0 && r.pos >= 0) {
+		if (r.n_cigar > 0 && vc_le32(cigar) == (r.l_seq << 4 | 4u) && r.tid >= 0 && r.pos >= 0) {
 			const uint8_t *words = nullptr;
 			uint32_t n_words = 0;
 			const int f = find_cg(seq + seq_bytes + r.l_seq, p + body, &words, &n_words);
@@ -390,7 +334,7 @@ bool VcBamReader::next_batch(std::vector<vc_bam_rec> &recs, std::vector<uint8_t>
 		if (r.n_cigar > 0) {
 			uint64_t qlen = 0;
 			for (uint32_t k = 0; k < r.n_cigar; ++k) {
-				const uint32_t c = le32(cigar + 4 * (size_t)k), op = c & 15;
+				const uint32_t c = vc_le32(cigar + 4 * (size_t)k), op = c & 15;
 				if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) qlen += c >> 4;
 			}
 			if (r.l_seq > 0 && !(r.flag & 4u) && qlen != r.l_seq) {

@@ -21,7 +21,7 @@
 
 // One group of consecutive blocks, inflated side by side into `text`.
 struct VcBgzfGroup {
-	std::vector<uint8_t> raw;      // compressed blocks, whole
+	std::vector<uint8_t> raw;      // compressed blocks, whole (and room for the next one read)
 	std::vector<uint32_t> boff;    // block i at raw[boff[i]], boff[n] = end
 	std::vector<uint32_t> toff;    // its text at text[toff[i]]
 	std::vector<uint8_t> text;

@@ -1,6 +1,6 @@
-// vafc_bgzf.h -- the BGZF member walk, shared by the host BAM reader
-// (vafc_bam.cpp), the device inflater's index (vc_bgzf_index, vafc_bgzf.hip) and
-// vcf-vaf-counter's BGZF pass (vafc_vcf.hip).  Plain C++, no zlib, no HIP.
+// vafc_bgzf.h -- the BGZF member walk over bytes in memory, shared by the
+// device inflater's index (vc_bgzf_index, vafc_bgzf.hip) and the host's member
+// reader (vafc_bgzf_io.h).  Plain C++, no zlib, no HIP.
 //
 // A BGZF member is a gzip member with FEXTRA set whose extra field holds a
 // subfield 'B' 'C' of two bytes: BSIZE, the member's whole size minus one.

@@ -18,10 +18,8 @@
 //                 the offset of the chr bytes, which are compared on a hash
 //                 match.  20,849 rows make 512 KB: it stays in L2.
 //
-//   BGZF input    (vc_vcf_count_file) is inflated on the device: compressed
-//                 members go over PCIe, the inflater's kernel (vafc_bgzf.hip)
-//                 writes the text into HBM and the two kernels above scan it
-//                 there; see count_bgzf_device below.
+// The handle (vafc_vcf_ctx.h) is created and scanned with here; the file
+// passes that feed the scans are vafc_vcf_files.cpp.
 //
 // Every global read is bounded: text by the bytes the tail kernel allows
 // (<= len; an aligned 16-byte load is issued only if it holds one of them, so
@@ -31,21 +29,12 @@
 // HIP failure is returned as VC_EHIP.
 #include <hip/hip_runtime.h>
 
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
-#include <zlib.h>
 
 #include <algorithm>
 #include <new>
-#include <string>
-#include <unordered_map>
-#include <vector>
 
-#include "vafc.h"
-#include "vafc_bgzf.h"
-#include "vafc_stage.h"
-#include "vafc_vcf.h"
+#include "vafc_vcf_ctx.h"
 
 namespace {
 
@@ -57,10 +46,6 @@ const uint32_t VCF_HALO = 256;   // bytes of the next tile staged with a tile: m
 static_assert(VCF_BLOCK * 16 == VC_VCF_TILE_BYTES, "a tile is one 16-byte load per lane");
 const uint32_t VCF_EMPTY = 0xFFFFFFFFu;
 const uint32_t VCF_MAX_CHR = 255;
-const size_t VCF_BLOCK_BYTES = (size_t)32 << 20;
-const size_t VCF_MAX_HITS = (size_t)1 << 20;
-// BGZF input without $VAFC_BGZF: inflated on the device (DESIGN 15 has the measurement that decided it)
-const bool VCF_BGZF_DEFAULT_DEVICE = true;
 
 struct VcVcfArgs {
 	const uint8_t *text;         // the block, any alignment
@@ -292,53 +277,7 @@ __global__ void __launch_bounds__(VCF_BLOCK) vcf_scan_kernel(VcVcfArgs A)
 	}
 }
 
-struct Pending {
-	const uint8_t *d_text = nullptr;
-	uint64_t len = 0, file_off = 0;
-	int final_block = 0;
-	hipStream_t st = nullptr;
-	bool active = false;
-};
-
-} // namespace
-
-struct vc_vcf : VcDevice {
-	uint32_t n_rows = 0;
-	VcDevBuf<uint4> d_table;
-	uint32_t mask = 0;
-	VcDevBuf<uint8_t> d_names;
-	VcDevBuf<uint16_t> d_row_ra;
-	VcDevBuf<uint4> d_hits;       // max_hits entries once a scan has run
-	size_t max_hits = VCF_MAX_HITS;
-	VcDevBuf<unsigned long long> d_n_hits;
-	VcDevBuf<uint64_t> d_consumed;
-	size_t block_bytes = VCF_BLOCK_BYTES;
-	Pending pend;
-	std::vector<vc_vcf_hit> acc;  // collected since the last vc_vcf_hits
-	bool handed = false;          // acc was returned: the next scan starts a new list
-	size_t last_consumed = 0;
-	uint64_t lines_reported = 0;
-	// the rows on the host, for the lines the device leaves to it
-	std::unordered_map<std::string, uint32_t> first_row;   // chr + '\t' + start
-	std::vector<uint16_t> row_ra;
-	// BGZF input inflated on the device (created by the first such file)
-	vc_bgzf *zf = nullptr;
-	VcDevBuf<uint8_t> ztext[2];   // the text of two pieces in turn, each behind `zhead` bytes of room for a tail
-	size_t zhead[2] = {0, 0};
-	uint64_t z_device_blocks = 0, z_host_blocks = 0;   // vc_vcf_inflate_info
-};
-
-namespace {
-
-std::string host_key(const char *chr, size_t len, int32_t start)
-{
-	std::string k(chr, len);
-	k.push_back('\t');
-	k += std::to_string(start);
-	return k;
-}
-
-int launch(vc_vcf *c, const Pending &p)
+int launch(vc_vcf *c, const VcVcfPending &p)
 {
 	if (c->d_hits.cap != c->max_hits) HIPCK(c->d_hits.grow(c->max_hits));   // max_hits >= 1
 	VcVcfArgs A;
@@ -408,7 +347,7 @@ int vcf_fill(vc_vcf *c, const char *const *chr, const int32_t *start, const char
 	c->row_ra.resize(n + 1, 0);
 	for (size_t i = 0; i < n; ++i) {
 		c->row_ra[i] = (uint16_t)((uint8_t)ref[i] | (uint16_t)(uint8_t)alt[i] << 8);
-		if (c->first_row.emplace(host_key(chr[i], strlen(chr[i]), start[i]), (uint32_t)i).second) firsts.push_back((uint32_t)i);
+		if (c->first_row.emplace(vcf_host_key(chr[i], strlen(chr[i]), start[i]), (uint32_t)i).second) firsts.push_back((uint32_t)i);
 	}
 	size_t slots = table_slots;
 	if (slots == 0)
@@ -509,19 +448,24 @@ int begin_scan(vc_vcf *c)
 	return VC_OK;
 }
 
+// Launch the scan of len device bytes on st; it is the pending one.
+int start_scan(vc_vcf *c, const uint8_t *d_text, size_t len, uint64_t file_off, int final, hipStream_t st)
+{
+	c->pend = VcVcfPending{d_text, len, file_off, final ? 1 : 0, st, false};
+	const int r = launch(c, c->pend);
+	c->pend.active = r == VC_OK;
+	return r;
+}
+
 } // namespace
 
 extern "C" int vc_vcf_scan_block(vc_vcf *c, const uint8_t *text, size_t len, uint64_t file_off, int final, size_t *consumed)
 {
 	if (!c || (len && !text)) return VC_EINVAL;
 	size_t cons = len;
-	if (!final) {
-		cons = 0;
-		for (size_t i = len; i > 0; --i)
-			if (text[i - 1] == '\n') {
-				cons = i;
-				break;
-			}
+	if (!final) {   // up to the last '\n'
+		const uint8_t *nl = len ? (const uint8_t *)memrchr(text, '\n', len) : nullptr;
+		cons = nl ? (size_t)(nl - text) + 1 : 0;
 	}
 	if (consumed) *consumed = cons;
 	int rc = begin_scan(c);
@@ -532,17 +476,8 @@ extern "C" int vc_vcf_scan_block(vc_vcf *c, const uint8_t *text, size_t len, uin
 	rc = c->stage.acquire_for(cons, 1, &s);
 	if (rc != VC_OK) return rc;
 	memcpy(s->h_seq, text, cons);
-	return c->stage.submit(cons, 1, c->st, [&](const VcSlot &sl) {
-		// only the consumed bytes are shipped, so on the device this block is final
-		c->pend.d_text = sl.d_seq;
-		c->pend.len = cons;
-		c->pend.file_off = file_off;
-		c->pend.final_block = 1;
-		c->pend.st = c->st;
-		const int r = launch(c, c->pend);
-		c->pend.active = r == VC_OK;
-		return r;
-	}, false);
+	// only the consumed bytes are shipped, so on the device this block is final
+	return c->stage.submit(cons, 1, c->st, [&](const VcSlot &sl) { return start_scan(c, sl.d_seq, cons, file_off, 1, c->st); }, false);
 }
 
 extern "C" int vc_vcf_scan_device(vc_vcf *c, const uint8_t *d_text, size_t len, uint64_t file_off, int final, void *stream)
@@ -552,16 +487,7 @@ extern "C" int vc_vcf_scan_device(vc_vcf *c, const uint8_t *d_text, size_t len, 
 	if (rc != VC_OK) return rc;
 	c->last_consumed = 0;
 	if (len == 0) return VC_OK;
-	return c->on_stream(stream, [&](hipStream_t st) {
-		c->pend.d_text = d_text;
-		c->pend.len = len;
-		c->pend.file_off = file_off;
-		c->pend.final_block = final ? 1 : 0;
-		c->pend.st = st;
-		const int r = launch(c, c->pend);
-		c->pend.active = r == VC_OK;
-		return r;
-	});
+	return c->on_stream(stream, [&](hipStream_t st) { return start_scan(c, d_text, len, file_off, final, st); });
 }
 
 extern "C" int vc_vcf_hits(vc_vcf *c, const vc_vcf_hit **hits, size_t *n_hits, size_t *consumed)
@@ -599,486 +525,4 @@ extern "C" int vc_vcf_set_block_bytes(vc_vcf *c, size_t bytes)
 extern "C" int vc_vcf_kernel_ms(vc_vcf *c, float *ms)
 {
 	return c ? c->timer.ms(ms) : VC_EINVAL;
-}
-
-namespace {
-
-// The lines a scan reported, in file order, under items 2-8: `text` holds the
-// scanned block from its byte `base` on, up to `consumed`; set(row, ref, alt)
-// receives item 7's assignments.  VC_OK (ended: a line ended the file), an
-// error of vc_vcf_eval_line, or VC_VCF_ABORTED.
-template <class Set>
-int eval_hits(vc_vcf *c, const vc_vcf_header *hdr, const uint8_t *text, size_t base, size_t consumed, uint64_t file_off,
-              const vc_vcf_hit *hits, size_t n_hits, int sample_idx, int min_depth, bool &ended, Set &&set)
-{
-	int rc = VC_OK;
-	const uint8_t *block = text - base;   // only bytes [base, consumed) of it are read
-	for (size_t i = 0; i < n_hits && !ended; ++i) {
-		const size_t lo = (size_t)(hits[i].off - file_off);
-		const uint8_t *nl = (const uint8_t *)memchr(block + lo, '\n', consumed - lo);
-		const size_t len = nl ? (size_t)(nl - block) - lo : consumed - lo;
-		vc_vcf_verdict v;
-		if ((rc = vc_vcf_eval_line(hdr, block + lo, len, sample_idx, min_depth, &v)) != VC_OK) break;
-		int64_t row = hits[i].row;
-		if (row < 0) {
-			if (!v.head_ok) {   // item 8: the file ends here
-				ended = true;
-				break;
-			}
-			// a line after all: matched here (items 2 and 3)
-			const auto it = c->first_row.find(host_key((const char *)block + lo, v.chrom_len, (int32_t)(uint32_t)(uint64_t)v.pos));
-			if (it == c->first_row.end()) continue;
-			if (v.n_allele != 2 || v.ref_len != 1 || v.alt_len != 1 ||
-			    c->row_ra[it->second] != (uint16_t)(v.ref | (uint16_t)v.alt << 8))
-				continue;
-			row = it->second;
-		}
-		if (v.verdict == VC_VCF_ABORT) {   // item 8: the reference's process ends here
-			rc = VC_VCF_ABORTED;
-			break;
-		}
-		if (v.verdict == VC_VCF_END) ended = true;
-		else if (v.verdict == VC_VCF_SET) set((size_t)row, v.ref_count, v.alt_count);
-	}
-	return rc;
-}
-
-// The pass with the text inflated (or read) on the host.
-int count_host(vc_vcf *c, const char *path, int kind, int sample_idx, int min_depth, int n_threads, uint32_t *counts,
-               vc_file_stats &st)
-{
-	VcVcfText in;
-	if (in.open(path, kind, n_threads) != VC_OK) {
-		fprintf(stderr, "Error: failed to open VCF file: %s\n", path);
-		return VC_EIO;
-	}
-	// the header: text is read until the #CHROM line is whole
-	std::vector<uint8_t> buf;
-	vc_vcf_header *hdr = nullptr;
-	size_t body = 0;
-	bool eof = false;
-	for (;;) {
-		const size_t at = buf.size(), step = (size_t)1 << 16;
-		buf.resize(at + step);
-		const size_t got = in.read(buf.data() + at, step);
-		buf.resize(at + got);
-		eof = got < step;
-		const int rc = vc_vcf_header_parse(buf.data(), buf.size(), eof, &hdr, &body);
-		if (rc == VC_OK) break;
-		if (rc != VC_VCF_MORE || eof) {
-			fprintf(stderr, "Error: failed to read VCF header\n");
-			return VC_EINVAL;
-		}
-	}
-	// what is read and not yet consumed: text[head ..), at file offset file_off
-	std::vector<uint8_t> text(buf.begin() + (ptrdiff_t)body, buf.end());
-	buf.clear();
-	buf.shrink_to_fit();
-	size_t head = 0;
-	uint64_t file_off = body;
-	st.bases = body;
-
-	int rc = VC_OK;
-	bool ended = false;
-	size_t cap = c->block_bytes;
-	while (!ended) {
-		// a block: up to cap bytes from a line start; one without a '\n' is a line
-		// longer than the block, which grows
-		if (head && (head >= text.size() / 2 || eof)) {
-			text.erase(text.begin(), text.begin() + (ptrdiff_t)head);
-			head = 0;
-		}
-		while (!eof && text.size() - head < cap) {
-			const size_t at = text.size(), want = cap - (at - head);
-			text.resize(at + want);
-			const size_t got = in.read(text.data() + at, want);
-			text.resize(at + got);
-			eof = got < want;
-		}
-		size_t blen = text.size() - head;
-		if (blen == 0) break;
-		if (blen > cap) blen = cap;
-		const bool final = eof && blen == text.size() - head;
-		const uint8_t *block = text.data() + head;
-		if (!final && !memchr(block, '\n', blen)) {
-			cap *= 2;
-			continue;
-		}
-		size_t consumed = 0;
-		if ((rc = vc_vcf_scan_block(c, block, blen, file_off, final ? 1 : 0, &consumed)) != VC_OK) break;
-		const vc_vcf_hit *hits = nullptr;
-		size_t n_hits = 0;
-		if ((rc = vc_vcf_hits(c, &hits, &n_hits, nullptr)) != VC_OK) break;
-		++st.blocks;
-		st.seqs += n_hits;
-		rc = eval_hits(c, hdr, block, 0, consumed, file_off, hits, n_hits, sample_idx, min_depth, ended,
-		               [&](size_t row, uint32_t ref, uint32_t alt) {
-			               counts[2 * row] = ref;
-			               counts[2 * row + 1] = alt;
-		               });
-		if (rc != VC_OK) break;
-		st.bases += consumed;
-		file_off += consumed;
-		head += consumed;
-	}
-	vc_vcf_header_free(hdr);
-	return rc;
-}
-
-// ---------------------------------------------------------------------------
-// BGZF input inflated on the device.  The header's members are inflated here
-// with zlib; from the member that holds the first data line on, pieces of
-// whole members are read straight into the stager's pinned slots, copied to
-// the device as they are and inflated there by the inflater's kernel
-// (vafc_bgzf.hip) on the inflater's stream, into one of two text buffers, while
-// the scan of the piece before runs on this handle's stream and its lines are
-// evaluated here.  A piece's text lies behind `zhead` free bytes of its buffer;
-// the unconsumed tail of the piece before is copied in front of it, so every
-// scan starts at a line start and reads one contiguous range.  The lines the
-// host evaluates reach it as one D2H copy of the scanned text from the first
-// reported line on (none when the scan reports nothing).
-//
-// VCF_FALLBACK: the file cannot be finished this way (a member whose status
-// is not 0, bytes that are no whole member before the end of the file, an
-// ISIZE above 65,536).  Nothing has been written to counts or stderr then.
-// ---------------------------------------------------------------------------
-const int VCF_FALLBACK = 100;
-const size_t VCF_ZHEAD = (size_t)1 << 20;         // room in front of a piece's text for the tail before it
-const size_t VCF_PIECE_BLOCKS = 65536;            // members of one piece at most
-
-// One member at the file position into dst (room for 65,536 bytes): 1 = read
-// (*m describes it), 0 = clean end of file, -1 = cut, not BGZF, or ISIZE too large.
-int read_member(FILE *fp, uint8_t *dst, VcBgzfMember *m)
-{
-	const size_t got = fread(dst, 1, VC_BGZF_HEAD, fp);
-	if (got == 0) return 0;
-	if (got != VC_BGZF_HEAD || !vc_bgzf_head_ok(dst)) return -1;
-	const size_t xlen = vc_bgzf_xlen(dst);
-	if (xlen && fread(dst + VC_BGZF_HEAD, 1, xlen, fp) != xlen) return -1;
-	const size_t size = vc_bgzf_member_size(dst + VC_BGZF_HEAD, xlen);
-	if (size == 0) return -1;
-	const size_t rest = size - VC_BGZF_HEAD - xlen;
-	if (fread(dst + VC_BGZF_HEAD + xlen, 1, rest, fp) != rest) return -1;
-	if (vc_bgzf_member_at(dst, size, m) != 1 || m->isize > VC_BGZF_MAX_TEXT) return -1;
-	return 1;
-}
-
-// zlib over one whole member, as the host reader checks it.
-bool inflate_member_host(const uint8_t *mem, const VcBgzfMember &m, std::vector<uint8_t> &text)
-{
-	const size_t at = text.size();
-	text.resize(at + m.isize + 1);
-	z_stream zs;
-	memset(&zs, 0, sizeof zs);
-	if (inflateInit2(&zs, -15) != Z_OK) return false;
-	zs.next_in = const_cast<uint8_t *>(mem + m.payload);
-	zs.avail_in = (uInt)m.payload_len;
-	zs.next_out = text.data() + at;
-	zs.avail_out = m.isize + 1;
-	const int rc = inflate(&zs, Z_FINISH);
-	const bool ok = rc == Z_STREAM_END && zs.total_out == m.isize;
-	inflateEnd(&zs);
-	text.resize(at + m.isize);
-	return ok && (uint32_t)crc32(crc32(0L, Z_NULL, 0), text.data() + at, m.isize) == m.crc32;
-}
-
-struct ZPiece {
-	size_t n_blocks = 0;
-	uint64_t text_len = 0;
-	bool last = false;        // the file ended behind it
-	int buf = 0;              // its text buffer
-};
-
-struct ZSet {
-	uint32_t row, ref, alt;
-};
-
-int count_bgzf_device(vc_vcf *c, const char *path, int sample_idx, int min_depth, uint32_t *counts, vc_file_stats &st)
-{
-	FILE *fp = fopen(path, "rb");
-	if (!fp) return VCF_FALLBACK;   // the host pass reports it
-	struct Closer {
-		FILE *fp;
-		vc_vcf_header *hdr = nullptr;
-		hipEvent_t ev = nullptr;
-		~Closer()
-		{
-			if (fp) fclose(fp);
-			vc_vcf_header_free(hdr);
-			if (ev) (void)hipEventDestroy(ev);
-		}
-	} own{fp};
-	HIPCK(hipSetDevice(c->dev));
-	if (!c->zf) {
-		const int rc = vc_bgzf_create(&c->zf, c->dev);
-		if (rc != VC_OK) return rc;
-	}
-	vc_bgzf *zf = c->zf;
-	const hipStream_t zst = (hipStream_t)vc_bgzf_stream(zf);
-	HIPCK(hipEventCreateWithFlags(&own.ev, hipEventDisableTiming));
-	uint64_t host_blocks = 0, device_blocks = 0;
-
-	// the header: members are inflated here until the #CHROM line is whole
-	std::vector<uint8_t> buf, mem(65536 + 16);
-	std::vector<uint64_t> toff(1, 0);   // text offset of each header member
-	std::vector<long> foff;             // ... and its file offset
-	size_t body = 0;
-	for (;;) {
-		const long at = ftell(fp);
-		VcBgzfMember m;
-		const int r = read_member(fp, mem.data(), &m);
-		if (r < 0) return VCF_FALLBACK;
-		const bool eof = r == 0;
-		if (!eof) {
-			if (!inflate_member_host(mem.data(), m, buf)) return VCF_FALLBACK;
-			foff.push_back(at);
-			toff.push_back(buf.size());
-			++host_blocks;
-		}
-		const int rc = vc_vcf_header_parse(buf.data(), buf.size(), eof, &own.hdr, &body);
-		if (rc == VC_OK) break;
-		// (the host pass says why: it sees the same text)
-		if (rc != VC_VCF_MORE || eof) return VCF_FALLBACK;
-	}
-	// the member that holds the first data line; the device starts over with it
-	size_t mb = 0;
-	while (mb + 1 < toff.size() && toff[mb + 1] <= body) ++mb;
-	const size_t skip = body - (size_t)toff[mb];   // bytes of its text in front of the first data line
-	if (mb < foff.size() && fseek(fp, foff[mb], SEEK_SET) != 0) return VCF_FALLBACK;
-	buf.clear();
-	buf.shrink_to_fit();
-
-	std::vector<ZSet> sets;   // item 7's assignments, applied once the file is known to be whole
-	std::vector<uint8_t> lines;
-	size_t cap = c->block_bytes;
-	ZPiece piece[2];
-	bool file_ended = false;
-
-	// Read the next piece into the stager's slot and send it on its way: H2D and
-	// inflate on the inflater's stream, into text buffer b behind its head room.
-	auto start_piece = [&](ZPiece &p, int b) -> int {
-		p = ZPiece();
-		p.buf = b;
-		if (file_ended) {
-			p.last = true;
-			return VC_OK;
-		}
-		const size_t raw_room = cap + 65536, max_blocks = std::min(VCF_PIECE_BLOCKS, raw_room / 28 + 1);
-		const size_t desc_at = (raw_room + 7) & ~(size_t)7;
-		VcSlot *s;
-		int rc = c->stage.acquire_for(desc_at + max_blocks * sizeof(vc_bgzf_block), 1, &s);
-		if (rc != VC_OK) return rc;
-		vc_bgzf_block *desc = reinterpret_cast<vc_bgzf_block *>(s->h_seq + desc_at);
-		size_t raw_len = 0;
-		while (p.text_len < cap && raw_len + 65536 <= raw_room && p.n_blocks < max_blocks) {
-			VcBgzfMember m;
-			const int r = read_member(fp, s->h_seq + raw_len, &m);
-			if (r < 0) return VCF_FALLBACK;
-			if (r == 0) {
-				file_ended = p.last = true;
-				break;
-			}
-			vc_bgzf_block &d = desc[p.n_blocks++];
-			d.in_off = raw_len + m.payload;
-			d.in_len = (uint32_t)m.payload_len;
-			d.isize = m.isize;
-			d.out_off = p.text_len;
-			d.crc32 = m.crc32;
-			d.reserved = 0;
-			p.text_len += m.isize;
-			raw_len += m.size;
-		}
-		if (p.n_blocks == 0) return VC_OK;
-		// the text buffer: nobody reads it any more but the copy of its tail, which `ev` follows
-		if (c->zhead[b] < VCF_ZHEAD) c->zhead[b] = VCF_ZHEAD;
-		if (c->ztext[b].cap < c->zhead[b] + p.text_len) HIPCK(c->ztext[b].grow(c->zhead[b] + (size_t)p.text_len + 65536));
-		HIPCK(hipStreamWaitEvent(zst, own.ev, 0));
-		uint8_t *d_text = c->ztext[b] + c->zhead[b];
-		const size_t nb = p.n_blocks;
-		const uint64_t tl = p.text_len;
-		// the descriptors travel with the compressed bytes: one copy of [0, desc_at + n * 32)
-		return c->stage.submit(desc_at + nb * sizeof(vc_bgzf_block), 1, zst, [&](const VcSlot &sl) {
-			return vc_bgzf_inflate_device(zf, sl.d_seq, raw_len, reinterpret_cast<const vc_bgzf_block *>(sl.d_seq + desc_at), nb,
-			                              d_text, (size_t)tl, VC_STREAM_CTX);
-		}, false);
-	};
-	// Whatever is in flight has ended before the buffers are left alone.
-	auto drain = [&]() {
-		(void)vc_bgzf_finish(zf, nullptr, 0, nullptr, nullptr);
-		(void)hipStreamSynchronize(c->st);
-		c->stage.settle();
-	};
-
-	HIPCK(hipEventRecord(own.ev, c->st));
-	int rc = start_piece(piece[0], 0);
-	if (rc != VC_OK) return drain(), rc;
-	uint64_t file_off = body;
-	st.bases = body;
-	size_t tail_len = 0, tail_at = 0;   // the unconsumed text of the piece before: ztext[tail_buf][tail_at, +tail_len)
-	int tail_buf = 0;
-	size_t first_skip = skip;
-	bool ended = false;
-	for (int k = 0; !ended; ++k) {
-		ZPiece &p = piece[k & 1];
-		const int b = p.buf;
-		if (p.n_blocks) {
-			size_t n = 0, ok = 0;
-			if ((rc = vc_bgzf_finish(zf, nullptr, 0, &n, &ok)) != VC_OK) break;
-			if (ok != p.n_blocks) {
-				rc = VCF_FALLBACK;
-				break;
-			}
-			device_blocks += p.n_blocks;
-		} else if (!p.last) {
-			rc = VC_EINVAL;   // (a piece without members is the end of the file)
-			break;
-		}
-		if (first_skip > p.text_len) {   // cannot be: the header's member is the piece's first
-			rc = VCF_FALLBACK;
-			break;
-		}
-		// the text to scan: the tail before, then this piece (the very first one from the first data line on)
-		size_t text_at = c->zhead[b] + first_skip, text_len = (size_t)p.text_len - first_skip;
-		first_skip = 0;
-		if (p.n_blocks == 0) {
-			// nothing new: what is left of the piece before is the file's last line
-			if (tail_len == 0) break;
-			text_at = tail_at;
-			text_len = tail_len;
-			p.buf = tail_buf;
-		} else if (tail_len) {
-			if (tail_len > c->zhead[b]) {
-				// a tail longer than the room in front of the text: a buffer with more room takes both
-				size_t room = c->zhead[b];
-				while (room < tail_len) room *= 2;
-				VcDevBuf<uint8_t> nb;
-				HIPCK(nb.alloc(room + (size_t)p.text_len + 65536));
-				HIPCK(hipMemcpyAsync(nb + room, c->ztext[b] + c->zhead[b], (size_t)p.text_len, hipMemcpyDeviceToDevice, c->st));
-				HIPCK(hipStreamSynchronize(c->st));
-				c->ztext[b] = std::move(nb);
-				c->zhead[b] = room;
-				text_at = room;
-			}
-			HIPCK(hipMemcpyAsync(c->ztext[b] + text_at - tail_len, c->ztext[tail_buf] + tail_at, tail_len, hipMemcpyDeviceToDevice,
-			                     c->st));
-			text_at -= tail_len;
-			text_len += tail_len;
-		}
-		HIPCK(hipEventRecord(own.ev, c->st));   // the other buffer's tail has left it
-		const int sb = p.buf;
-		const bool final = p.last;
-		// the text is scanned as the host pass scans it: in blocks of up to cap bytes from a line start (a block
-		// without a '\n' grows), a block shorter than cap only at the end of the file
-		size_t pos = 0;
-		bool next_started = false;
-		while (!ended && pos < text_len) {
-			size_t blen = text_len - pos;
-			if (blen < cap && !final) break;   // the rest waits for the next piece
-			if (blen > cap) blen = cap;
-			const bool final_block = final && pos + blen == text_len;
-			const uint8_t *d_text = c->ztext[sb] + text_at + pos;
-			if ((rc = vc_vcf_scan_device(c, d_text, blen, file_off, final_block ? 1 : 0, VC_STREAM_CTX)) != VC_OK) break;
-			// the next piece is read, copied and inflated while this one is scanned and evaluated
-			if (!next_started && (rc = start_piece(piece[(k + 1) & 1], sb ^ 1)) != VC_OK) break;
-			next_started = true;
-			const vc_vcf_hit *hits = nullptr;
-			size_t n_hits = 0, consumed = 0;
-			if ((rc = vc_vcf_hits(c, &hits, &n_hits, &consumed)) != VC_OK) break;
-			if (consumed == 0 && !final_block) {   // no '\n': a line longer than the block
-				cap *= 2;
-				continue;
-			}
-			++st.blocks;
-			st.seqs += n_hits;
-			if (n_hits) {
-				const size_t lo = (size_t)(hits[0].off - file_off);
-				lines.resize(consumed - lo);
-				HIPCK(hipMemcpy(lines.data(), d_text + lo, consumed - lo, hipMemcpyDeviceToHost));
-				rc = eval_hits(c, own.hdr, lines.data(), lo, consumed, file_off, hits, n_hits, sample_idx, min_depth, ended,
-				               [&](size_t row, uint32_t ref, uint32_t alt) { sets.push_back(ZSet{(uint32_t)row, ref, alt}); });
-				if (rc != VC_OK) break;
-			}
-			st.bases += consumed;
-			file_off += consumed;
-			pos += consumed;
-		}
-		if (rc != VC_OK || ended || final) break;
-		if (!next_started && (rc = start_piece(piece[(k + 1) & 1], sb ^ 1)) != VC_OK) break;
-		tail_buf = sb;
-		tail_at = text_at + pos;
-		tail_len = text_len - pos;
-	}
-	drain();
-	if (rc == VCF_FALLBACK || (rc != VC_OK && rc != VC_VCF_ABORTED)) return rc;
-	for (const ZSet &z : sets) {
-		counts[2 * (size_t)z.row] = z.ref;
-		counts[2 * (size_t)z.row + 1] = z.alt;
-	}
-	c->z_device_blocks = device_blocks;
-	c->z_host_blocks = host_blocks;
-	return rc;
-}
-
-// Whole BGZF members of a file, by their headers alone.
-uint64_t count_members(const char *path)
-{
-	FILE *fp = fopen(path, "rb");
-	if (!fp) return 0;
-	uint64_t n = 0;
-	uint8_t h[VC_BGZF_HEAD + 65536];
-	for (;;) {
-		if (fread(h, 1, VC_BGZF_HEAD, fp) != VC_BGZF_HEAD || !vc_bgzf_head_ok(h)) break;
-		const size_t xlen = vc_bgzf_xlen(h);
-		if (xlen && fread(h + VC_BGZF_HEAD, 1, xlen, fp) != xlen) break;
-		const size_t size = vc_bgzf_member_size(h + VC_BGZF_HEAD, xlen);
-		if (size == 0 || fseek(fp, (long)(size - VC_BGZF_HEAD - xlen), SEEK_CUR) != 0) break;
-		++n;
-	}
-	fclose(fp);
-	return n;
-}
-
-} // namespace
-
-extern "C" int vc_vcf_inflate_info(const vc_vcf *c, uint64_t *device_blocks, uint64_t *host_blocks)
-{
-	if (!c) return VC_EINVAL;
-	if (device_blocks) *device_blocks = c->z_device_blocks;
-	if (host_blocks) *host_blocks = c->z_host_blocks;
-	return VC_OK;
-}
-
-extern "C" int vc_vcf_count_file(vc_vcf *c, const char *path, int sample_idx, int min_depth, int n_threads, uint32_t *counts,
-                                 vc_file_stats *stats)
-{
-	if (!c || !path || (c->n_rows && !counts)) return VC_EINVAL;
-	const double t0 = vc_now();
-	vc_file_stats st;
-	memset(&st, 0, sizeof st);
-	if (stats) *stats = st;
-	c->z_device_blocks = c->z_host_blocks = 0;
-	int kind = VC_VCF_OTHER;
-	if (vc_vcf_probe(path, &kind) != VC_OK) {
-		fprintf(stderr, "Error: failed to open VCF file: %s\n", path);
-		return VC_EIO;
-	}
-	if (kind == VC_VCF_BCF) {
-		fprintf(stderr, "Error: %s is %s; only VCF text (plain, gzip or BGZF) is read\n", path, vc_vcf_kind_name(kind));
-		return VC_EINVAL;
-	}
-	int rc = VCF_FALLBACK;
-	if (kind == VC_VCF_BGZF) {
-		// $VAFC_BGZF = host | device; unset: VCF_BGZF_DEFAULT_DEVICE
-		const char *e = getenv("VAFC_BGZF");
-		const bool device = e && *e ? strcmp(e, "device") == 0 : VCF_BGZF_DEFAULT_DEVICE;
-		if (device) rc = count_bgzf_device(c, path, sample_idx, min_depth, counts, st);
-		if (rc == VCF_FALLBACK) {
-			memset(&st, 0, sizeof st);
-			c->z_host_blocks = count_members(path);
-		}
-	}
-	if (rc == VCF_FALLBACK) rc = count_host(c, path, kind, sample_idx, min_depth, n_threads, counts, st);
-	st.seconds = vc_now() - t0;
-	if (stats) *stats = st;
-	return rc;
 }

@@ -132,7 +132,7 @@ def test_header_and_lines_across_members(block, matcher, tmp_path, bgzf_env):
             for path in ("device", "host"):
                 bgzf_env(path)
                 counts, st = matcher.count_file(str(tmp_path / "x.vcf.gz"), s, d)
-                got[path] = (pairs_of(counts), st.bases, st.seqs)
+                got[path] = (pairs_of(counts), st.bases, st.seqs, st.blocks)
                 assert pairs_of(counts) == want, (path, s, d)
                 assert st.bases == len(text)
                 info = matcher.inflate_info()
@@ -195,6 +195,109 @@ def test_damaged_files_give_what_the_host_path_gives(kind, tmp_path, matcher, bg
     assert counts.any()
     bgzf_env("host")
     assert pairs_of(matcher.count_file(str(tmp_path / "d.vcf.gz"))[0]) == pairs_of(counts)
+
+
+def head_walk(data: bytes) -> int:
+    """Members by their heads alone, as vc_vcf_inflate_info counts them after a fallback: the fixed bytes, the extra
+    field, a BSIZE that can hold both and the trailer, then a seek past the body (whether or not it is there)."""
+    n = at = 0
+    while len(data) - at >= 12 and data[at:at + 3] == b"\x1f\x8b\x08" and data[at + 3] & 4:
+        xlen = int.from_bytes(data[at + 10:at + 12], "little")
+        extra = data[at + 12:at + 12 + xlen]
+        if len(extra) != xlen:
+            break
+        bsize, i = None, 0
+        while i + 4 <= xlen and bsize is None:
+            slen = int.from_bytes(extra[i + 2:i + 4], "little")
+            if extra[i:i + 2] == b"BC" and slen == 2 and i + 6 <= xlen:
+                bsize = int.from_bytes(extra[i + 4:i + 6], "little")
+            i += 4 + slen
+        if bsize is None or bsize + 1 < 12 + xlen + 8:
+            break
+        at += bsize + 1
+        n += 1
+    return n
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,members", [("wrong_crc", 24), ("flipped_bit", 24), ("cut", 16), ("gzip_member_inside", 11),
+                                          ("isize_65537", 25), ("trailing_bytes", 24)])
+def test_host_blocks_after_a_fallback_is_the_head_walk(kind, members, tmp_path, matcher, bgzf_env):
+    """A member whose head is whole counts even when its body is cut (`cut`: 16, not the 15 whole members)."""
+    data = damaged_files()[kind]
+    assert head_walk(data) == members
+    (tmp_path / "d.vcf.gz").write_bytes(data)
+    bgzf_env("device")
+    matcher.count_file(str(tmp_path / "d.vcf.gz"))
+    assert matcher.inflate_info() == (0, members)
+
+
+def both_paths(matcher, bgzf_env, path, text, blocks):
+    """Counts, st.bases and st.seqs of the device path are the host path's at every block size, and the counts
+    process_vcf's; inflate_info of the device path at the last block size."""
+    want, _ = F.process_vcf(ROWS, text, 0, 1)
+    info = None
+    try:
+        for block in blocks:
+            matcher.set_block_bytes(block)
+            got = {}
+            for p in ("device", "host"):
+                bgzf_env(p)
+                counts, st = matcher.count_file(path)
+                got[p] = (pairs_of(counts), st.bases, st.seqs)
+                assert pairs_of(counts) == want and st.bases == len(text), (p, block)
+                if p == "device":
+                    info = tuple(matcher.inflate_info())
+            assert got["device"] == got["host"], block
+    finally:
+        matcher.set_block_bytes(32 << 20)
+    return want, info
+
+
+def header_and_body():
+    text = golden("main.vcf") + F.synth_vcf(ROWS, 40, 2, seed=9, hit_rate=0.2, header_too=False)
+    body_off = text.index(b"\n", text.index(b"\n#CHROM") + 1) + 1
+    return text[:body_off], text[body_off:]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("empty_between", [False, True])
+def test_first_data_line_at_a_members_first_byte(empty_between, matcher, tmp_path, bgzf_env):
+    """The header ends with a member: the device starts behind the header's members, with nothing to skip."""
+    header, body = header_and_body()
+    data = B.bgzf_bytes(header, 6, 150, eof=False) + (B.EOF_MEMBER.raw() if empty_between else b"") + B.bgzf_bytes(body, 6, 150)
+    assert len(data) < 10_000
+    (tmp_path / "b.vcf.gz").write_bytes(data)
+    want, info = both_paths(matcher, bgzf_env, str(tmp_path / "b.vcf.gz"), header + body, [1, 4096])
+    assert any(p != (0, 0) for p in want)
+    assert info[0] > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("eof", [True, False])
+def test_header_and_no_data_line(eof, matcher, tmp_path, bgzf_env):
+    """Nothing to scan: all counts zero.  The device path finished: a fallback would report (0, every member of
+    the file), the EOF member among them; without one the file gives the device nothing to inflate."""
+    header, _ = header_and_body()
+    (tmp_path / "h.vcf.gz").write_bytes(B.bgzf_bytes(header, 6, 150, eof=eof))
+    want, info = both_paths(matcher, bgzf_env, str(tmp_path / "h.vcf.gz"), header, [4096])
+    assert all(p == (0, 0) for p in want)
+    assert info == ((1 if eof else 0), -(-len(header) // 150))
+
+
+@pytest.mark.gpu
+def test_last_line_without_newline_across_pieces(matcher, tmp_path, bgzf_env):
+    """The unterminated last line arrives as the tail of the piece before an empty last piece."""
+    head = golden("nonl.vcf")
+    n_samples = len(head[head.index(b"\n#CHROM") + 1:].split(b"\n")[0].split(b"\t")) - 9
+    more = F.synth_vcf(ROWS, 8, n_samples, seed=5, hit_rate=0.5, header_too=False)
+    text = head + b"\n" + more[:-1]
+    assert 200 < len(more) < 1000 and more.endswith(b"\n") and not text.endswith(b"\n")
+    data = B.bgzf_bytes(text, 6, 150)
+    assert len(data) < 10_000
+    (tmp_path / "n.vcf.gz").write_bytes(data)
+    want, info = both_paths(matcher, bgzf_env, str(tmp_path / "n.vcf.gz"), text, [1, 64, 1000])
+    assert any(p != (0, 0) for p in want) and info[0] > 0
 
 
 @pytest.mark.gpu

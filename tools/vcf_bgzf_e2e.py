@@ -8,7 +8,9 @@ The file: a VCF header, then a seeded chunk of 100-sample lines
 holds at least --bytes of text, then the EOF member.  --parent is the parent
 commit's vcf-vaf-counter (built from a checkout of it into a directory of its
 own), --branch this tree's (default lib/vcf-vaf-counter, run with
-VAFC_BGZF=device; --branch-host adds a leg with VAFC_BGZF=host).  The runs
+VAFC_BGZF=device; --branch-host adds a leg with VAFC_BGZF=host, --parent-host
+the parent's binary under VAFC_BGZF=host, against which that leg is held by
+the same rule: host_within).  The runs
 alternate parent, branch, parent, ... --runs times each after one untimed run
 of each; the wall clock of each process is taken with a host clock, and the
 .vaf files must be identical.  One JSON object: the seconds of every run, the
@@ -83,6 +85,7 @@ def main():
     ap.add_argument("--parent", required=True)
     ap.add_argument("--branch", default=os.path.join(ROOT, "kmer-cnt_amd", "lib", "vcf-vaf-counter"))
     ap.add_argument("--branch-host", action="store_true")
+    ap.add_argument("--parent-host", action="store_true")
     ap.add_argument("--bytes", type=int, default=2 << 30)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--out")
@@ -96,6 +99,8 @@ def main():
         legs = [("parent", a.parent, None), ("branch", a.branch, "device")]
         if a.branch_host:
             legs.append(("branch_host", a.branch, "host"))
+        if a.parent_host:
+            legs.append(("parent_host", a.parent, "host"))
         secs = {name: [] for name, _b, _e in legs}
         shas = set()
         for i in range(a.runs + 1):
@@ -111,6 +116,9 @@ def main():
                median={k: median(v) for k, v in secs.items()}, parent_spread=round(spread, 4), vaf_sha256=shas.pop(),
                vaf_identical=True)
     res["device_default"] = res["median"]["branch"] <= res["median"]["parent"] + spread
+    if a.parent_host and a.branch_host:
+        res["parent_host_spread"] = round(max(secs["parent_host"]) - min(secs["parent_host"]), 4)
+        res["host_within"] = res["median"]["branch_host"] <= res["median"]["parent_host"] + res["parent_host_spread"]
     res["text_GBps"] = {k: round(text_bytes / v / 1e9, 3) for k, v in res["median"].items()}
     print(json.dumps(res))
     if a.out:
