@@ -718,13 +718,89 @@ int vc_bam_set_counts(vc_bam *b, const uint32_t *counts);
  * counts do not depend on it. */
 int vc_bam_set_long_threshold(vc_bam *b, uint32_t ops);
 int vc_bam_kernel_ms(vc_bam *b, float *ms);
+
+/* Records found, checked and counted in inflated BAM text on the device: the
+ * text never reaches the host.  A text is a piece of a file's record stream
+ * (behind the header): a chain in which the record at offset o, with its
+ * block_size word bl, is followed by the one at o + 4 + bl.
+ *
+ *  - entry: the offset of the piece's first record (<= text_bytes).  cuts: n
+ *    offsets, ascending, each <= text_bytes, that divide the text into n + 1
+ *    segments (the file pass uses the BGZF members' borders); they decide how
+ *    the work is shared out and never what is found.  Each segment guesses
+ *    its first record start (a run of plausible headers: block_size >= 32,
+ *    -1 <= tid, next_tid < the handle's n_refs, pos >= -1, l_read_name >= 1,
+ *    l_seq >= 0, fields that fit, a NUL at the name's end) and walks from it;
+ *    one wave then links the segments in order from `entry`, walking again
+ *    every segment whose guess is not the true entry, so the records are
+ *    those of the serial walk whatever the guesses were.
+ *  - The walk takes a record when its block_size is >= 32 and it lies whole
+ *    inside the text.  It stops at a block_size < 32 (short_stop) and at a
+ *    record the text cuts off; `consumed` is the offset where it stopped, or
+ *    text_bytes.  A caller with more text scans the next piece from there;
+ *    with final != 0 the records end there (item 7: a cut record ends the
+ *    file).
+ *  - Each record found gets the tests of the host reader.  It is irregular,
+ *    and not counted, when its fields do not fit its block_size, l_read_name
+ *    = 0, l_seq < 0, its CIGAR's query length is not l_seq (n_cigar > 0,
+ *    l_seq > 0, flag 0x4 clear), or its first CIGAR word is l_seq << 4 | 4
+ *    with tid >= 0, pos >= 0 and aux bytes behind the qualities (the CG
+ *    long-CIGAR convention: the tag may be among them).  With final
+ *    != 0 a cut last record whose 36 leading bytes are there and whose fields
+ *    do not fit is irregular too.  The host reader drops such records and
+ *    reads on elsewhere (item 7), so a caller that sees irregular > 0 or
+ *    short_stop and wants the contract's counts reads the file on the host.
+ *  - Every other record is counted where it lies, under items 2 to 6, the
+ *    regions of vc_bam_set_regions and the long threshold included, by the
+ *    kernels of vc_bam_count_block; counts accumulate as there.
+ *
+ * text_bytes < 2^32 - 16.  Every device read is bounded by text_bytes.
+ * vc_bam_scan_text_device: text and cuts in HBM (cuts 8-byte aligned) on
+ * `stream`, with vc_count_device's ordering contract; both stay valid until
+ * the stream has passed the call.  vc_bam_scan_text_block: host bytes staged
+ * through pinned memory, asynchronous, buffers reusable on return.
+ * vc_bam_text_result waits for the handle's stream and reports the last scan.
+ * vc_bam_text_kernel_ms: the last scan's guess, link and emit launches
+ * (find_ms) and its check kernel (check_ms), either may be NULL; the count
+ * kernels behind them are vc_bam_kernel_ms. */
+typedef struct {
+	uint64_t consumed;
+	uint64_t records;        /* regular records: counted */
+	uint64_t bases;          /* the sum of their l_seq */
+	uint64_t irregular_off;  /* lowest offset of an irregular record, UINT64_MAX without one */
+	uint32_t irregular;
+	uint32_t rewalked;       /* segments whose guess was not their true entry */
+	uint32_t short_stop;
+	uint32_t found;          /* records found, the irregular ones among them */
+} vc_bam_text_res;
+int vc_bam_scan_text_device(vc_bam *b, const uint8_t *d_text, size_t text_bytes, uint64_t entry, const uint64_t *d_cuts,
+                            size_t n_cuts, int final, void *stream);
+int vc_bam_scan_text_block(vc_bam *b, const uint8_t *text, size_t text_bytes, uint64_t entry, const uint64_t *cuts,
+                           size_t n_cuts, int final);
+int vc_bam_text_result(vc_bam *b, vc_bam_text_res *res);
+int vc_bam_text_kernel_ms(vc_bam *b, float *find_ms, float *check_ms);
+
 /* count_bam_variants (bam-vaf-counter.c:417-470) for one file: its own stderr
  * lines, the regions and weights of items 5 and 6 from this file's header and
  * index, every record through the kernels.  n_threads inflate BGZF blocks.
  * VC_EIO: cannot be opened; VC_EINVAL: not BGZF BAM or no readable header
  * (nothing counted in both cases).  st: seqs = records, bases = sum of l_seq,
- * blocks = batches. */
+ * blocks = batches.
+ *
+ * By default, and with $VAFC_BGZF = device, the members behind the header are copied down
+ * compressed, inflated by vc_bgzf_inflate_device and read by
+ * vc_bam_scan_text_device, in pieces of whole members; only the counts come
+ * back.  The pass gives up, puts the handle's counts back to what they were
+ * before the file and leaves the file to the host reader at a member that
+ * does not inflate, bytes that are no whole member, an ISIZE above 65,536, an
+ * irregular record, a short block_size, or a record longer than a text
+ * buffer: the result on such files is the host reader's, and n_threads sizes
+ * it.  $VAFC_BGZF = host: the host reader alone (DESIGN 16 has the
+ * measurement that decided the default).  vc_bam_inflate_info: the members of the last file that were
+ * inflated on the host (header members of a device pass among them) and on
+ * the device (0 after a fallback). */
 int vc_bam_count_file(vc_bam *b, const char *path, int n_threads, vc_file_stats *st);
+int vc_bam_inflate_info(const vc_bam *b, uint64_t *host_members, uint64_t *device_members);
 
 /* ------------------------------------------------------------------ */
 /* vcf-vaf-counter: genotypes of a VCF as .vaf counts                  */

@@ -101,7 +101,17 @@ int main(int argc, char *argv[])
 			return 1;
 		}
 		// a file that cannot be opened, or whose header cannot be read, is reported and skipped
-		rc = vc_bam_count_file(bam, fn, n_thread, nullptr);
+		vc_file_stats fst;
+		rc = vc_bam_count_file(bam, fn, n_thread, &fst);
+		// VAFC_PHASES=1: where the file's BGZF members were inflated (all on the
+		// host after a device pass that gave the file up) and what was read
+		if (getenv("VAFC_PHASES") && rc == VC_OK) {
+			uint64_t hm = 0, dm = 0;
+			(void)vc_bam_inflate_info(bam, &hm, &dm);
+			fprintf(stderr, "[P::main] %s: inflate host %llu device %llu members, %llu records, %llu bases, %.4f s\n", fn,
+			        (unsigned long long)hm, (unsigned long long)dm, (unsigned long long)fst.seqs,
+			        (unsigned long long)fst.bases, fst.seconds);
+		}
 		if (rc != VC_OK && rc != VC_EIO && rc != VC_EINVAL) {
 			fprintf(stderr, "Error: counting failed on %s (%s)\n", fn, vc_strerror(rc));
 			vc_bam_destroy(bam);

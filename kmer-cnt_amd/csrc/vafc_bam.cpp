@@ -31,6 +31,7 @@ bool VcBgzf::open(const char *path, int n_threads)
 	cur_ = 0;
 	pos_ = 0;
 	carry_.clear();
+	members_ = 0;
 	return true;
 }
 
@@ -79,6 +80,7 @@ void VcBgzf::load(VcBgzfGroup *g)
 	while (good < n && ok[good]) ++good;
 	if (good < n) g->last = true;
 	g->text_len = g->toff[good];
+	members_ += good;
 }
 
 bool VcBgzf::advance()

@@ -13,6 +13,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <atomic>
 #include <future>
 #include <string>
 #include <vector>
@@ -37,8 +38,11 @@ public:
 	// The next n bytes of text, contiguous (valid until the next call), or
 	// NULL when fewer are left before the end of the stream.
 	const uint8_t *take(size_t n);
+	// Members inflated so far, the group read ahead included.
+	uint64_t members() const { return members_.load(); }
 
 private:
+	std::atomic<uint64_t> members_{0};
 	void load(VcBgzfGroup *g);     // read and inflate the next group
 	bool advance();                // make `cur` the next group
 	FILE *fp_ = nullptr;
@@ -64,6 +68,7 @@ public:
 	// Offsets are relative to data[0] and multiples of 4.
 	bool next_batch(std::vector<vc_bam_rec> &recs, std::vector<uint8_t> &data, size_t max_bytes, size_t max_recs);
 	uint64_t bases = 0, records = 0;
+	uint64_t members() const { return z_.members(); }   // BGZF members inflated for it
 
 private:
 	VcBgzf z_;

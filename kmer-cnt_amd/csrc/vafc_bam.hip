@@ -23,6 +23,14 @@
 // CIGAR words are read as aligned dwords (offsets are multiples of 4), bases
 // as bytes.
 //
+//   text          vc_bam_scan_text_*: records found and checked in inflated BAM
+//                 text on the device (vafc_bam_text.h: guess, link, emit, check,
+//                 four launches on one stream) and counted where they lie by a
+//                 second instantiation of the two kernels, whose CIGAR loads are
+//                 byte loads: a record starts at any offset of the text
+//
+// vc_bam_count_file and its device pass over BGZF members: vafc_bam_files.cpp.
+//
 // Nothing here counts on the CPU: any HIP failure is returned as VC_EHIP.
 #include <hip/hip_runtime.h>
 
@@ -39,6 +47,8 @@
 
 #include "vafc.h"
 #include "vafc_bam.h"
+#include "vafc_bam_ctx.h"
+#include "vafc_bam_text.h"
 #include "vafc_stage.h"
 
 namespace {
@@ -46,6 +56,7 @@ namespace {
 struct VcBamArgs {
 	const vc_bam_rec *recs;
 	uint64_t n_recs;
+	const uint32_t *n_found;     // text scans: the number of records is on the device (NULL: n_recs)
 	const uint8_t *data;
 	uint64_t data_bytes;
 	const uint64_t *row_key;     // [n_rows] bam_key(tid, pos), ascending
@@ -89,11 +100,20 @@ __device__ inline bool bam_ref_op(uint32_t op) { return op == 0 || op == 2 || op
 __device__ inline bool bam_query_op(uint32_t op) { return op == 0 || op == 1 || op == 4 || op == 7 || op == 8; }
 __device__ inline bool bam_match_op(uint32_t op) { return op == 0 || op == 7 || op == 8; }
 
-// The record's CIGAR and bases lie inside data, on a 4-byte boundary.
-__device__ inline bool bam_in_bounds(const vc_bam_rec &r, uint64_t data_bytes)
+// The record's CIGAR and bases lie inside data, on a 4-byte boundary unless
+// the record lies in text (ALIGNED false).
+template <bool ALIGNED> __device__ inline bool bam_in_bounds(const vc_bam_rec &r, uint64_t data_bytes)
 {
 	const uint64_t need = 4 * (uint64_t)r.n_cigar + (((uint64_t)r.l_seq + 1) >> 1);
-	return (r.off & 3) == 0 && r.off <= data_bytes && need <= data_bytes - r.off;
+	return (!ALIGNED || (r.off & 3) == 0) && r.off <= data_bytes && need <= data_bytes - r.off;
+}
+
+// CIGAR word k of the words at cig: one dword, or four bytes at any alignment.
+template <bool ALIGNED> __device__ inline uint32_t bam_cig(const uint8_t *cig, uint32_t k)
+{
+	if (ALIGNED) return reinterpret_cast<const uint32_t *>(cig)[k];
+	const uint8_t *p = cig + 4 * (size_t)k;
+	return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
 }
 
 // Item 6: merged regions [s, e) of this tid with s < end and e > pos.
@@ -118,12 +138,12 @@ __device__ inline void bam_hit(const VcBamArgs &A, uint32_t j, const uint8_t *se
 	else if (base == alt) atomicAdd(&A.counts[2 * (size_t)info.x + 1], w);
 }
 
-__global__ void __launch_bounds__(BAM_BLOCK) bam_short_kernel(VcBamArgs A)
+template <bool ALIGNED> __device__ inline void bam_short_body(const VcBamArgs &A)
 {
 	const uint64_t i = (uint64_t)blockIdx.x * BAM_BLOCK + threadIdx.x;
-	if (i >= A.n_recs) return;
+	if (i >= A.n_recs || (A.n_found && i >= *A.n_found)) return;
 	const vc_bam_rec r = A.recs[i];
-	if (!bam_in_bounds(r, A.data_bytes)) {
+	if (!bam_in_bounds<ALIGNED>(r, A.data_bytes)) {
 		atomicOr(A.flags, 1u);
 		return;
 	}
@@ -135,11 +155,11 @@ __global__ void __launch_bounds__(BAM_BLOCK) bam_short_kernel(VcBamArgs A)
 	const uint64_t tid_end = bam_key(r.tid, BAM_POS_END);
 	uint32_t j = bam_lower(A.row_key, A.n_rows, bam_key(r.tid, r.pos));
 	if (j >= A.n_rows || A.row_key[j] > tid_end) return;   // most records: no row at or after them
-	const uint32_t *cig = reinterpret_cast<const uint32_t *>(A.data + r.off);
+	const uint8_t *cig = A.data + r.off;
 	const uint8_t *seq = A.data + r.off + 4 * (size_t)r.n_cigar;
 	int64_t rlen = 0;
 	for (uint32_t k = 0; k < r.n_cigar; ++k) {
-		const uint32_t c = cig[k];
+		const uint32_t c = bam_cig<ALIGNED>(cig, k);
 		if (bam_ref_op(c & 15u)) rlen += c >> 4;
 	}
 	int64_t end = (int64_t)r.pos + (rlen ? rlen : 1);
@@ -158,7 +178,7 @@ __global__ void __launch_bounds__(BAM_BLOCK) bam_short_kernel(VcBamArgs A)
 		const int64_t p = bam_key_pos(key);
 		uint32_t op = 0, len = 0;
 		for (; k < r.n_cigar; ++k) {
-			const uint32_t c = cig[k];
+			const uint32_t c = bam_cig<ALIGNED>(cig, k);
 			op = c & 15u;
 			len = c >> 4;
 			if (bam_ref_op(op)) {
@@ -172,6 +192,9 @@ __global__ void __launch_bounds__(BAM_BLOCK) bam_short_kernel(VcBamArgs A)
 	}
 }
 
+__global__ void __launch_bounds__(BAM_BLOCK) bam_short_kernel(VcBamArgs A) { bam_short_body<true>(A); }
+__global__ void __launch_bounds__(BAM_BLOCK) bam_short_text_kernel(VcBamArgs A) { bam_short_body<false>(A); }
+
 // Inclusive scan over the wave's 64 lanes.
 __device__ inline uint64_t bam_wave_scan(uint64_t v, int lane)
 {
@@ -183,20 +206,20 @@ __device__ inline uint64_t bam_wave_scan(uint64_t v, int lane)
 	return v;
 }
 
-__global__ void __launch_bounds__(BAM_BLOCK) bam_long_kernel(VcBamArgs A)
+template <bool ALIGNED> __device__ inline void bam_long_body(const VcBamArgs &A)
 {
 	const int lane = threadIdx.x & 63;
 	const uint32_t waves = gridDim.x * (BAM_BLOCK / 64);
 	const uint32_t n_long = *A.long_n;
 	for (uint32_t e = blockIdx.x * (BAM_BLOCK / 64) + (threadIdx.x >> 6); e < n_long; e += waves) {
 		const vc_bam_rec r = A.recs[A.long_list[e]];   // listed by the short kernel: in bounds, not skipped
-		const uint32_t *cig = reinterpret_cast<const uint32_t *>(A.data + r.off);
+		const uint8_t *cig = A.data + r.off;
 		const uint8_t *seq = A.data + r.off + 4 * (size_t)r.n_cigar;
 		uint32_t w = 1;
 		if (A.n_reg) {
 			uint64_t rl = 0;
 			for (uint32_t k = (uint32_t)lane; k < r.n_cigar; k += 64) {
-				const uint32_t c = cig[k];
+				const uint32_t c = bam_cig<ALIGNED>(cig, k);
 				if (bam_ref_op(c & 15u)) rl += c >> 4;
 			}
 #pragma unroll
@@ -210,7 +233,7 @@ __global__ void __launch_bounds__(BAM_BLOCK) bam_long_kernel(VcBamArgs A)
 		uint64_t base_rp = 0;
 		for (uint32_t g = 0; g < r.n_cigar; g += 64) {
 			const uint32_t k = g + (uint32_t)lane;
-			const uint32_t c = k < r.n_cigar ? cig[k] : 0xFu;   // past the end: a reserved op, it does nothing
+			const uint32_t c = k < r.n_cigar ? bam_cig<ALIGNED>(cig, k) : 0xFu;   // past the end: a reserved op, it does nothing
 			const uint32_t op = c & 15u, len = c >> 4;
 			const uint64_t radv = bam_ref_op(op) ? len : 0, qadv = bam_query_op(op) ? len : 0;
 			const uint64_t rsum = bam_wave_scan(radv, lane), qsum = bam_wave_scan(qadv, lane);
@@ -232,36 +255,142 @@ __global__ void __launch_bounds__(BAM_BLOCK) bam_long_kernel(VcBamArgs A)
 	}
 }
 
-// records and data bytes of one batch of vc_bam_count_file ($VAFC_BATCH_BYTES: vc_batch_bytes)
-const size_t BAM_BATCH_BYTES = (size_t)32 << 20;
-const size_t BAM_BATCH_RECS = (size_t)1 << 19;
+__global__ void __launch_bounds__(BAM_BLOCK) bam_long_kernel(VcBamArgs A) { bam_long_body<true>(A); }
+__global__ void __launch_bounds__(BAM_BLOCK) bam_long_text_kernel(VcBamArgs A) { bam_long_body<false>(A); }
+
+// ---------------------------------------------------------------------------
+// Records in text (vafc_bam_text.h has the method and its bounds)
+// ---------------------------------------------------------------------------
+
+struct VcBamTextArgs {
+	const uint8_t *text;
+	uint64_t len;
+	const uint64_t *cuts;   // [n_cuts], ascending
+	uint32_t n_cuts;
+	int32_t n_ref;
+	uint64_t entry;         // the piece's first record
+	uint32_t final;
+	uint32_t max_recs;      // room in offs and recs
+	VbtSeg *segs;           // [n_cuts + 1]
+	uint32_t *offs;         // [max_recs] record offsets, in no order
+	vc_bam_rec *recs;       // [max_recs] descriptor of offs[i]
+	VbtResult *res;
+};
+
+// One lane per segment: its guess and the walk from there.
+__global__ void __launch_bounds__(BAM_BLOCK) bam_text_guess_kernel(VcBamTextArgs T)
+{
+	const uint64_t s = (uint64_t)blockIdx.x * BAM_BLOCK + threadIdx.x;
+	if (s > T.n_cuts) return;
+	uint64_t a, b;
+	vbt_seg_range(T.cuts, T.n_cuts, T.len, (uint32_t)s, &a, &b);
+	VbtSeg sg;
+	sg.entry = vbt_guess(T.text, T.len, a, b, T.n_ref);
+	sg.exit = 0;
+	sg.count = sg.stop = 0;
+	if (sg.entry != VBT_NONE) vbt_walk(T.text, T.len, sg.entry, b, &sg, nullptr, 0);
+	T.segs[s] = sg;
+}
+
+// One wave, the segments in order, 64 at a time: each lane loads one segment,
+// and every lane takes the same steps on the values of segment j, so a segment
+// that is walked again is walked by the whole wave on the same addresses.
+__global__ void __launch_bounds__(64) bam_text_link_kernel(VcBamTextArgs T)
+{
+	const int lane = threadIdx.x;
+	const uint32_t n_seg = T.n_cuts + 1;
+	uint64_t e = T.entry;
+	uint32_t stop = VBT_STOP_NONE, rewalked = 0;
+	for (uint32_t base = 0; base < n_seg; base += 64) {
+		const uint32_t s = base + (uint32_t)lane;
+		VbtSeg mine;
+		mine.entry = VBT_NONE;
+		mine.exit = 0;
+		mine.count = mine.stop = 0;
+		uint64_t a = 0, b = 0;
+		if (s < n_seg) {
+			mine = T.segs[s];
+			vbt_seg_range(T.cuts, T.n_cuts, T.len, s, &a, &b);
+		}
+		const int m = n_seg - base < 64 ? (int)(n_seg - base) : 64;
+		for (int j = 0; j < m; ++j) {
+			VbtSeg sg;
+			sg.entry = __shfl((unsigned long long)mine.entry, j, 64);
+			sg.exit = __shfl((unsigned long long)mine.exit, j, 64);
+			sg.count = __shfl(mine.count, j, 64);
+			sg.stop = __shfl(mine.stop, j, 64);
+			const uint64_t ja = __shfl((unsigned long long)a, j, 64), jb = __shfl((unsigned long long)b, j, 64);
+			vbt_link_step(T.text, T.len, ja, jb, &sg, &e, &stop, &rewalked);
+			if (lane == j) mine = sg;
+		}
+		if (s < n_seg) T.segs[s] = mine;
+	}
+	if (lane == 0) vbt_link_end(T.text, T.len, e, stop, T.final != 0, rewalked, T.res);
+}
+
+// One lane per segment: the offsets of its records, from its true entry, into
+// slots reserved with one atomic.
+__global__ void __launch_bounds__(BAM_BLOCK) bam_text_emit_kernel(VcBamTextArgs T)
+{
+	const uint64_t s = (uint64_t)blockIdx.x * BAM_BLOCK + threadIdx.x;
+	if (s > T.n_cuts) return;
+	const VbtSeg sg = T.segs[s];
+	if (sg.entry == VBT_NONE || sg.count == 0) return;
+	uint64_t a, b;
+	vbt_seg_range(T.cuts, T.n_cuts, T.len, (uint32_t)s, &a, &b);
+	const uint32_t at = atomicAdd(&T.res->n_found, sg.count);
+	if ((uint64_t)at + sg.count > T.max_recs) return;   // cannot be: the records are disjoint and 36 bytes or more each
+	VbtSeg again;
+	vbt_walk(T.text, T.len, sg.entry, b, &again, T.offs + at, sg.count);
+}
+
+// One lane per record found: its descriptor, or the skipped one of an
+// irregular record; the totals per wave.
+__global__ void __launch_bounds__(BAM_BLOCK) bam_text_check_kernel(VcBamTextArgs T)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * BAM_BLOCK + threadIdx.x;
+	const uint32_t n = T.res->n_found < T.max_recs ? T.res->n_found : T.max_recs;
+	unsigned long long regular = 0, bases = 0;
+	if (i < n) {
+		const uint64_t o = T.offs[i];
+		vc_bam_rec r;
+		if (vbt_check(T.text, o, &r)) {
+			regular = 1;
+			bases = r.l_seq;
+		} else {
+			vbt_skip_rec(&r);
+			atomicAdd(&T.res->irr_n, 1u);
+			atomicMin((unsigned long long *)&T.res->irr_off, (unsigned long long)o);
+		}
+		T.recs[i] = r;
+	}
+#pragma unroll
+	for (int d = 32; d > 0; d >>= 1) {
+		regular += __shfl_xor(regular, d, 64);
+		bases += __shfl_xor(bases, d, 64);
+	}
+	if ((threadIdx.x & 63) == 0 && regular) {
+		atomicAdd((unsigned long long *)&T.res->records, regular);
+		atomicAdd((unsigned long long *)&T.res->bases, bases);
+	}
+}
 
 } // namespace
 
-struct vc_bam : VcDevice {
-	uint32_t n_pat = 0, n_rows = 0;
-	VcDevBuf<uint64_t> d_row_key;
-	VcDevBuf<uint2> d_row_info;
-	VcDevBuf<uint32_t> d_counts, d_flags;   // 2 * n_pat + 2, 1
-	VcDevBuf<uint64_t> d_reg_s, d_reg_e;    // one capacity (vc_bam_set_regions)
-	uint32_t n_reg = 0;
-	VcDevBuf<uint32_t> d_long_list, d_long_n;
-	uint32_t long_thr = 64;
-	// the rows as build_regions sees them: merged regions by chromosome name
-	std::vector<std::string> reg_chr;
-	std::vector<int32_t> reg_start, reg_end;
-};
-
 namespace {
 
-int launch(vc_bam *c, const vc_bam_rec *d_recs, uint64_t n_recs, const uint8_t *d_data, size_t data_bytes, hipStream_t st)
+// n_found: the device's count of the descriptors (a text scan: n_recs is their
+// room, and the records lie at any alignment).
+int launch(vc_bam *c, const vc_bam_rec *d_recs, uint64_t n_recs, const uint8_t *d_data, size_t data_bytes, hipStream_t st,
+           const uint32_t *n_found = nullptr)
 {
 	if (n_recs == 0) return VC_OK;
-	if (n_recs > 0xFFFFFFFFull || ((uintptr_t)d_recs & 7) || ((uintptr_t)d_data & 3)) return VC_EINVAL;
+	if (n_recs > 0xFFFFFFFFull || ((uintptr_t)d_recs & 7) || (!n_found && ((uintptr_t)d_data & 3))) return VC_EINVAL;
 	if (n_recs > c->d_long_list.cap) HIPCK(c->d_long_list.grow(n_recs + n_recs / 4 + 1024));
 	VcBamArgs A;
 	A.recs = d_recs;
 	A.n_recs = n_recs;
+	A.n_found = n_found;
 	A.data = d_data;
 	A.data_bytes = data_bytes;
 	A.row_key = c->d_row_key;
@@ -278,12 +407,12 @@ int launch(vc_bam *c, const vc_bam_rec *d_recs, uint64_t n_recs, const uint8_t *
 	HIPCK(c->d_long_n.zero_async(st));
 	HIPCK(c->timer.begin(st));
 	const unsigned grid = (unsigned)((n_recs + BAM_BLOCK - 1) / BAM_BLOCK);
-	hipLaunchKernelGGL(bam_short_kernel, dim3(grid), dim3(BAM_BLOCK), 0, st, A);
+	hipLaunchKernelGGL(n_found ? bam_short_text_kernel : bam_short_kernel, dim3(grid), dim3(BAM_BLOCK), 0, st, A);
 	HIPCK(hipGetLastError());
 	// the list's length is known on the device only: a fixed grid of waves walks it
 	uint64_t lgrid = (uint64_t)c->n_cu * 2;
 	if (lgrid > (n_recs + 3) / 4) lgrid = (n_recs + 3) / 4;
-	hipLaunchKernelGGL(bam_long_kernel, dim3((unsigned)lgrid), dim3(BAM_BLOCK), 0, st, A);
+	hipLaunchKernelGGL(n_found ? bam_long_text_kernel : bam_long_kernel, dim3((unsigned)lgrid), dim3(BAM_BLOCK), 0, st, A);
 	HIPCK(hipGetLastError());
 	HIPCK(c->timer.end(st));
 	return VC_OK;
@@ -351,7 +480,51 @@ int bam_fill(vc_bam *c, const vc_patterns *db, const char *const *ref_names, int
 	HIPCK(c->d_flags.zero());
 	HIPCK(c->d_long_n.alloc(1));
 	HIPCK(c->d_long_n.zero());
+	HIPCK(c->d_tres.alloc(1));
+	HIPCK(c->d_tres.zero());
+	HIPCK(c->text_timer.init());
+	HIPCK(c->check_timer.init());
+	c->n_ref = n_refs;
 	return VC_OK;
+}
+
+// The four launches of a text scan and the two count kernels behind them, on
+// st; d_cuts is read by them, so it stays until st has passed them.
+int scan_text(vc_bam *c, const uint8_t *d_text, size_t text_bytes, uint64_t entry, const uint64_t *d_cuts, size_t n_cuts,
+              int final, hipStream_t st)
+{
+	if (text_bytes > 0xFFFFFFF0ull || n_cuts > 0x7FFFFFFFull || entry > text_bytes) return VC_EINVAL;
+	const size_t n_seg = n_cuts + 1, max_recs = text_bytes / VBT_FIXED + 1;
+	if (n_seg > c->d_segs.cap) HIPCK(c->d_segs.grow(n_seg + n_seg / 4 + 64));
+	if (max_recs > c->d_offs.cap) HIPCK(c->d_offs.grow(max_recs + max_recs / 4 + 1024, c->d_trecs, max_recs + max_recs / 4 + 1024));
+	VcBamTextArgs T;
+	T.text = d_text;
+	T.len = text_bytes;
+	T.cuts = d_cuts;
+	T.n_cuts = (uint32_t)n_cuts;
+	T.n_ref = c->n_ref;
+	T.entry = entry;
+	T.final = final ? 1u : 0u;
+	T.max_recs = (uint32_t)max_recs;
+	T.segs = c->d_segs;
+	T.offs = c->d_offs;
+	T.recs = c->d_trecs;
+	T.res = c->d_tres;
+	HIPCK(c->d_tres.zero_async(st));
+	HIPCK(c->text_timer.begin(st));
+	const unsigned sgrid = (unsigned)((n_seg + BAM_BLOCK - 1) / BAM_BLOCK), rgrid = (unsigned)((max_recs + BAM_BLOCK - 1) / BAM_BLOCK);
+	hipLaunchKernelGGL(bam_text_guess_kernel, dim3(sgrid), dim3(BAM_BLOCK), 0, st, T);
+	HIPCK(hipGetLastError());
+	hipLaunchKernelGGL(bam_text_link_kernel, dim3(1), dim3(64), 0, st, T);
+	HIPCK(hipGetLastError());
+	hipLaunchKernelGGL(bam_text_emit_kernel, dim3(sgrid), dim3(BAM_BLOCK), 0, st, T);
+	HIPCK(hipGetLastError());
+	HIPCK(c->text_timer.end(st));
+	HIPCK(c->check_timer.begin(st));
+	hipLaunchKernelGGL(bam_text_check_kernel, dim3(rgrid), dim3(BAM_BLOCK), 0, st, T);
+	HIPCK(hipGetLastError());
+	HIPCK(c->check_timer.end(st));
+	return launch(c, c->d_trecs, max_recs, d_text, text_bytes, st, &c->d_tres.p->n_found);
 }
 
 } // namespace
@@ -379,6 +552,9 @@ extern "C" void vc_bam_destroy(vc_bam *c)
 {
 	if (!c) return;
 	c->close();
+	c->text_timer.destroy();
+	c->check_timer.destroy();
+	vc_bgzf_destroy(c->zf);
 	delete c;
 }
 
@@ -482,71 +658,69 @@ extern "C" int vc_bam_kernel_ms(vc_bam *c, float *ms)
 	return c ? c->timer.ms(ms) : VC_EINVAL;
 }
 
-extern "C" int vc_bam_count_file(vc_bam *c, const char *path, int n_threads, vc_file_stats *stats)
+extern "C" int vc_bam_scan_text_device(vc_bam *c, const uint8_t *d_text, size_t text_bytes, uint64_t entry,
+                                       const uint64_t *d_cuts, size_t n_cuts, int final, void *stream)
 {
-	if (!c || !path) return VC_EINVAL;
-	const double t0 = vc_now();
-	vc_file_stats st;
-	memset(&st, 0, sizeof st);
-	if (stats) *stats = st;
-	VcBamReader rd;
-	int rc = rd.open(path, n_threads);
-	if (rc == VC_EIO) {
-		fprintf(stderr, "Error: failed to open BAM file: %s\n", path);
-		return rc;
-	}
-	if (rc != VC_OK) {
-		int kind = VC_BAM_BGZF;
-		if (vc_bam_probe(path, &kind) == VC_OK && kind == VC_BAM_BGZF) fprintf(stderr, "Error: failed to read BAM header\n");
-		return rc;
-	}
-	// count_bam_variants :436-458: regions are used only beside an index
-	const bool have_regions = !c->reg_chr.empty();
-	const bool have_index = vc_bam_index_usable(path, nullptr, 0) != 0;
-	std::vector<int32_t> tid, start, end;
-	if (!have_index || !have_regions) {
-		if (!have_index)
-			fprintf(stderr, "[M::%s] Warning: failed to load BAM index for %s, processing all reads\n", "count_bam_variants", path);
-		if (!have_regions)
-			fprintf(stderr, "[M::%s] Warning: no target regions available, processing all reads\n", "count_bam_variants");
-	} else {
-		fprintf(stderr, "[M::%s] Using indexed access to fetch reads from %d target regions\n", "count_bam_variants",
-		        (int)c->reg_chr.size());
-		std::unordered_map<std::string, int32_t> tid_of;
-		for (size_t i = 0; i < rd.refs().size(); ++i) tid_of.emplace(rd.refs()[i], (int32_t)i);
-		for (size_t i = 0; i < c->reg_chr.size(); ++i) {
-			const auto it = tid_of.find(c->reg_chr[i]);
-			if (it == tid_of.end()) {
-				fprintf(stderr, "Warning: chromosome %s not found in BAM\n", c->reg_chr[i].c_str());
-				continue;
-			}
-			tid.push_back(it->second);
-			start.push_back(c->reg_start[i]);
-			end.push_back(c->reg_end[i]);
-		}
-	}
-	const bool weighted = have_index && have_regions;
-	rc = vc_bam_set_regions(c, tid.data(), start.data(), end.data(), tid.size());
-	if (rc != VC_OK) return rc;
-	if (weighted && tid.empty()) {
-		// every region is on a chromosome this file lacks: the reference fetches nothing
-		st.seconds = vc_now() - t0;
-		if (stats) *stats = st;
-		return VC_OK;
-	}
-	const size_t limit = vc_batch_bytes(BAM_BATCH_BYTES);
-	std::vector<vc_bam_rec> recs;
-	std::vector<uint8_t> data;
-	for (;;) {
-		recs.clear();
-		data.clear();
-		if (!rd.next_batch(recs, data, limit, BAM_BATCH_RECS)) break;
-		if ((rc = vc_bam_count_block(c, recs.data(), recs.size(), data.data(), data.size())) != VC_OK) break;
-		++st.blocks;
-	}
-	st.bases = rd.bases;
-	st.seqs = rd.records;
-	st.seconds = vc_now() - t0;
-	if (stats) *stats = st;
-	return rc;
+	if (!c || (text_bytes && !d_text) || (n_cuts && !d_cuts) || ((uintptr_t)d_cuts & 7)) return VC_EINVAL;
+	HIPCK(hipSetDevice(c->dev));
+	return c->on_stream(stream, [&](hipStream_t st) { return scan_text(c, d_text, text_bytes, entry, d_cuts, n_cuts, final, st); });
 }
+
+extern "C" int vc_bam_scan_text_block(vc_bam *c, const uint8_t *text, size_t text_bytes, uint64_t entry, const uint64_t *cuts,
+                                      size_t n_cuts, int final)
+{
+	if (!c || (text_bytes && !text) || (n_cuts && !cuts)) return VC_EINVAL;
+	for (size_t i = 0; i < n_cuts; ++i)
+		if (cuts[i] > text_bytes || (i && cuts[i] < cuts[i - 1])) return VC_EINVAL;
+	HIPCK(hipSetDevice(c->dev));
+	// the text first, the cuts behind it on an 8-byte boundary
+	const size_t cuts_at = (text_bytes + 7) & ~(size_t)7, total = cuts_at + n_cuts * sizeof(uint64_t) + 8;
+	VcSlot *s;
+	const int rc = c->stage.acquire_for(total, 1, &s);
+	if (rc != VC_OK) return rc;
+	if (text_bytes) memcpy(s->h_seq, text, text_bytes);
+	if (n_cuts) memcpy(s->h_seq + cuts_at, cuts, n_cuts * sizeof(uint64_t));
+	return c->stage.submit(total, 1, c->st, [&](const VcSlot &sl) {
+		return scan_text(c, sl.d_seq, text_bytes, entry, reinterpret_cast<const uint64_t *>(sl.d_seq + cuts_at), n_cuts, final, c->st);
+	}, false);
+}
+
+int vc_bam_scan_text_cuts(vc_bam *c, const uint8_t *d_text, size_t text_bytes, uint64_t entry, const uint64_t *cuts,
+                          size_t n_cuts, int final)
+{
+	if (n_cuts > c->d_cuts.cap) HIPCK(c->d_cuts.grow(n_cuts + n_cuts / 4 + 64));
+	// pageable source: the copy has left the caller's buffer on return
+	if (n_cuts) HIPCK(hipMemcpyAsync(c->d_cuts, cuts, n_cuts * sizeof(uint64_t), hipMemcpyHostToDevice, c->st));
+	return scan_text(c, d_text, text_bytes, entry, c->d_cuts, n_cuts, final, c->st);
+}
+
+extern "C" int vc_bam_text_result(vc_bam *c, vc_bam_text_res *res)
+{
+	if (!c || !res) return VC_EINVAL;
+	HIPCK(hipSetDevice(c->dev));
+	HIPCK(hipStreamSynchronize(c->st));
+	VbtResult r;
+	HIPCK(hipMemcpy(&r, c->d_tres, sizeof r, hipMemcpyDeviceToHost));
+	res->consumed = r.consumed;
+	res->records = r.records;
+	res->bases = r.bases;
+	res->irregular_off = r.irr_off;
+	res->irregular = r.irr_n;
+	res->rewalked = r.rewalked;
+	res->short_stop = r.short_stop;
+	res->found = r.n_found;
+	return VC_OK;
+}
+
+extern "C" int vc_bam_text_kernel_ms(vc_bam *c, float *find_ms, float *check_ms)
+{
+	if (!c) return VC_EINVAL;
+	float f = 0, k = 0;
+	int rc = c->text_timer.ms(&f);
+	if (rc == VC_OK) rc = c->check_timer.ms(&k);
+	if (rc != VC_OK) return rc;
+	if (find_ms) *find_ms = f;
+	if (check_ms) *check_ms = k;
+	return VC_OK;
+}
+

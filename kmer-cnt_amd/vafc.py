@@ -59,7 +59,8 @@ EXPORTS = (
     "vc_bam_file_ref_name", "vc_bam_file_records", "vc_bam_file_free", "vc_bam_index_usable", "vc_bam_build_regions",
     "vc_bam_create", "vc_bam_destroy", "vc_bam_set_regions", "vc_bam_count_block", "vc_bam_count_device",
     "vc_bam_finish", "vc_bam_reset", "vc_bam_set_counts", "vc_bam_set_long_threshold", "vc_bam_kernel_ms",
-    "vc_bam_count_file",
+    "vc_bam_count_file", "vc_bam_scan_text_device", "vc_bam_scan_text_block", "vc_bam_text_result",
+    "vc_bam_text_kernel_ms", "vc_bam_inflate_info",
     "vc_vcf_probe", "vc_vcf_kind_name", "vc_vcf_header_parse", "vc_vcf_header_samples", "vc_vcf_header_type",
     "vc_vcf_header_free", "vc_vcf_eval_line", "vc_vcf_create", "vc_vcf_create_raw", "vc_vcf_destroy",
     "vc_vcf_scan_block", "vc_vcf_scan_device", "vc_vcf_hits", "vc_vcf_set_max_hits", "vc_vcf_set_block_bytes",
@@ -263,6 +264,11 @@ def lib():
         "vc_bam_set_long_threshold": (C.c_int, [P, C.c_uint32]),
         "vc_bam_kernel_ms": (C.c_int, [P, C.POINTER(C.c_float)]),
         "vc_bam_count_file": (C.c_int, [P, C.c_char_p, C.c_int, C.POINTER(FileStats)]),
+        "vc_bam_scan_text_device": (C.c_int, [P, P, C.c_size_t, C.c_uint64, P, C.c_size_t, C.c_int, P]),
+        "vc_bam_scan_text_block": (C.c_int, [P, P, C.c_size_t, C.c_uint64, P, C.c_size_t, C.c_int]),
+        "vc_bam_text_result": (C.c_int, [P, P]),
+        "vc_bam_text_kernel_ms": (C.c_int, [P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+        "vc_bam_inflate_info": (C.c_int, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "vc_vcf_probe": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
         "vc_vcf_kind_name": (C.c_char_p, [C.c_int]),
         "vc_vcf_header_parse": (C.c_int, [P, C.c_size_t, C.c_int, C.POINTER(P), C.POINTER(C.c_size_t)]),
@@ -1546,6 +1552,16 @@ def build_regions(db: PatternDB):
     return out
 
 
+class BamTextResult(C.Structure):
+    """vc_bam_text_res: the outcome of the last text scan."""
+    _fields_ = [("consumed", C.c_uint64), ("records", C.c_uint64), ("bases", C.c_uint64),
+                ("irregular_off", C.c_uint64), ("irregular", C.c_uint32), ("rewalked", C.c_uint32),
+                ("short_stop", C.c_uint32), ("found", C.c_uint32)]
+
+
+BAM_NO_IRREGULAR = 0xFFFFFFFFFFFFFFFF     # BamTextResult.irregular_off without an irregular record
+
+
 class BamCounter:
     """Ref/alt base counts at the rows' positions over BAM records on the GPU
     (worker_check_positions, bam-vaf-counter.c:290-318).  ref_names: the
@@ -1615,6 +1631,43 @@ class BamCounter:
         ms = C.c_float()
         _ck(lib().vc_bam_kernel_ms(self._h, C.byref(ms)), "vc_bam_kernel_ms")
         return ms.value
+
+    def scan_text_block(self, text, entry: int = 0, cuts=(), final: bool = True) -> None:
+        """Find, check and count the records of inflated BAM text (host bytes)
+        on the GPU: entry = the offset of its first record, cuts = ascending
+        offsets that divide the work.  Asynchronous; text_result() reports."""
+        text = np.frombuffer(bytes(text), np.uint8) if isinstance(text, (bytes, bytearray)) else \
+            np.ascontiguousarray(text, dtype=np.uint8)
+        cuts = np.ascontiguousarray(cuts, dtype=np.uint64)
+        _ck(lib().vc_bam_scan_text_block(self._h, _ptr(text) if text.size else None, text.size, entry,
+                                         _ptr(cuts) if cuts.size else None, cuts.size, 1 if final else 0),
+            "vc_bam_scan_text_block")
+
+    def scan_text_device(self, text_ptr: int, text_bytes: int, entry: int = 0, cuts_ptr: int = 0, n_cuts: int = 0,
+                         final: bool = True, stream: int = 0) -> None:
+        """The same for HBM-resident text and cuts (uint64) on `stream`."""
+        _ck(lib().vc_bam_scan_text_device(self._h, P(text_ptr) if text_ptr else None, text_bytes, entry,
+                                          P(cuts_ptr) if cuts_ptr else None, n_cuts, 1 if final else 0,
+                                          P(stream) if stream else None), "vc_bam_scan_text_device")
+
+    def text_result(self) -> "BamTextResult":
+        """Waits for the handle's stream: what the last text scan found."""
+        res = BamTextResult()
+        _ck(lib().vc_bam_text_result(self._h, C.byref(res)), "vc_bam_text_result")
+        return res
+
+    def text_kernel_ms(self):
+        """(find ms, check ms) of the last text scan: guess + link + emit, and
+        the check kernel; the count kernels behind them are kernel_ms()."""
+        find, check = C.c_float(), C.c_float()
+        _ck(lib().vc_bam_text_kernel_ms(self._h, C.byref(find), C.byref(check)), "vc_bam_text_kernel_ms")
+        return find.value, check.value
+
+    def inflate_info(self):
+        """(host members, device members) of the last count_file."""
+        h, d = C.c_uint64(), C.c_uint64()
+        _ck(lib().vc_bam_inflate_info(self._h, C.byref(h), C.byref(d)), "vc_bam_inflate_info")
+        return h.value, d.value
 
     def close(self):
         if getattr(self, "_h", None):
