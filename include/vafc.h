@@ -631,7 +631,7 @@ int vc_ed_count_file(vc_ed *ed, const char *path, int n_threads, vc_file_stats *
  *    :124-175): one [pos, pos + 1) per row, sorted by strcmp(chr) then start,
  *    merged while prev.end >= next.start; a region's tid is looked up in THIS
  *    file's header, regions on an absent chromosome warn and are skipped.  The
- *    whole file is read and w applied; nothing seeks.
+ *    whole file is read and w applied; nothing seeks, but under item 9.
  * 7. What ends a file's records, keeping those before, silently and with exit
  *    code 0.  A BGZF block that is truncated, does not inflate or fails its
  *    CRC-32 / ISIZE, and a record cut off by the end of the data, end them
@@ -652,7 +652,26 @@ int vc_ed_count_file(vc_ed *ed, const char *path, int n_threads, vc_file_stats *
  * 8. Deviations: BGZF-compressed BAM only; a base index at or past l_seq
  *    counts nothing (so l_seq == 0 with a CIGAR counts nothing); a record in
  *    the CG:B,I long-CIGAR convention is counted with its real CIGAR, as
- *    htslib moves it in; htslib's own [E::/[W:: lines are not reproduced. */
+ *    htslib moves it in; htslib's own [E::/[W:: lines are not reproduced.
+ * 9. The seek plan (vc_bam_index_plan), for a BAI index and item 6's merged
+ *    regions (tid, s, e).  Per region: the bins of [s, e) in the 6-level,
+ *    14-bit scheme (reg2bins); of their chunks (beg, end as virtual offsets,
+ *    compressed offset << 16 | offset in the member's text) those with end >
+ *    min_off, min_off the linear index's entry of window s >> 14, or 0 where
+ *    the linear index is shorter.  The union over all regions is sorted by
+ *    beg and merged while the next span's beg >> 16 is <= the current span's
+ *    end >> 16, so the spans ascend, no BGZF member belongs to two of them and
+ *    no record is read twice.  A span is read from the record at beg through
+ *    the last record that starts before end.  This is a superset of what
+ *    htslib's iterator returns for the regions; item 6's weights and the
+ *    kernels' own overlap test make the counts those of the whole file.  The
+ *    index is not usable for seeking when it is no BAI (a CSI among them), is
+ *    truncated, carries a count its length cannot hold or bytes behind
+ *    n_no_coor, has an n_ref other than the header's, a bin twice in one
+ *    reference or a chunk with end < beg, or when a region ends past 2^29.  An
+ *    index that passes all this and belongs to another file is not detected:
+ *    as with the reference, the counts are then those of whatever records
+ *    the stale offsets lead to. */
 
 /* One record as the kernels read it: its n_cigar CIGAR words (BAM encoding,
  * len << 4 | op) at data + off, off a multiple of 4, followed by its (l_seq +
@@ -691,6 +710,20 @@ int vc_bam_index_usable(const char *path, char *buf, size_t buf_len);
  * open a merged region, its end in ends[]; both arrays hold
  * vc_patterns_count entries, the return value is the number of regions. */
 int vc_bam_build_regions(const vc_patterns *db, int32_t *first_row, int32_t *ends);
+/* Item 9's plan, no GPU: the spans to read for n merged regions (tid in [0,
+ * n_ref), 0 <= start < end) by the BAI at index_path, or, with index_path
+ * NULL, by the index item 6 finds for bam_path.  n_ref: the references of the
+ * BAM's header.  VC_OK: *spans holds *n_spans spans, ascending and disjoint
+ * (NULL and 0 where no chunk is wanted), to be freed by
+ * vc_bam_index_plan_free.  VC_BAM_NO_SEEK: there is no index, or it is not
+ * usable for seeking.  VC_EINVAL: a bad argument or region. */
+typedef struct {
+	uint64_t beg, end;     /* virtual offsets */
+} vc_bam_span;
+#define VC_BAM_NO_SEEK 1
+int vc_bam_index_plan(const char *bam_path, const char *index_path, int32_t n_ref, const int32_t *tid, const int32_t *start,
+                      const int32_t *end, size_t n, vc_bam_span **spans, size_t *n_spans);
+void vc_bam_index_plan_free(vc_bam_span *spans);
 
 /* A counter for the rows of db, their tids from ref_names[0..n_refs) (the
  * first file's header, create_snp_map :187-215, whose two warnings are
@@ -780,6 +813,60 @@ int vc_bam_scan_text_block(vc_bam *b, const uint8_t *text, size_t text_bytes, ui
 int vc_bam_text_result(vc_bam *b, vc_bam_text_res *res);
 int vc_bam_text_kernel_ms(vc_bam *b, float *find_ms, float *check_ms);
 
+/* Many short record chains of one text walked in one launch: what a seeking
+ * pass has after it inflated the members of its spans back to back.  A piece
+ * is a chain whose first record the index gives: the walk starts at `entry`
+ * and takes every record that starts before `stop` and lies whole below
+ * `limit`, the end of the piece's own text, under the text scan's walk rule (a
+ * record is a block_size >= 32).  limit is clamped to text_bytes, entry and
+ * stop to limit; entry >= stop is an empty piece.  One lane walks one piece.
+ *
+ * A piece ends VC_BAM_PIECE_OK; _CUT, when a record that starts before stop
+ * runs past limit (missing: the bytes of it that lie past limit, 0 where not
+ * even its block_size word is whole); _SHORT at a block_size < 32; or _NOROOM,
+ * when the pieces overlap so far that their records outnumber text_bytes / 36
+ * + 1.  Only the records of OK pieces are emitted: each is checked and counted
+ * as a record of a text scan is (irregular ones are not counted), in no
+ * particular order.  `found` of a piece that did not end OK is the number of
+ * records before the one that stopped it.  A caller that sees a cut piece
+ * walks it again with more text; one that wants the contract's counts and sees
+ * short, irregular or noroom reads the file another way.
+ *
+ * text_bytes < 2^32 - 16.  Every device read of the text is below the piece's
+ * clamped limit.  vc_bam_scan_pieces_device: text and pieces (8-byte aligned)
+ * in HBM on `stream`, with vc_count_device's ordering contract.
+ * vc_bam_scan_pieces_block: host bytes staged through pinned memory.
+ * vc_bam_pieces_result waits for the handle's stream and reports the last
+ * piece scan: the totals, the first n_status per-piece outcomes in the
+ * pieces' order, and the first n_offs emitted record offsets (a piece's own
+ * are offs[first .. first + found), ascending); either array may be NULL.
+ * vc_bam_text_kernel_ms reports the walk as find_ms. */
+typedef struct {
+	uint64_t entry, stop, limit;
+} vc_bam_piece;
+enum { VC_BAM_PIECE_OK = 0, VC_BAM_PIECE_CUT = 1, VC_BAM_PIECE_SHORT = 2, VC_BAM_PIECE_NOROOM = 3 };
+typedef struct {
+	uint32_t status;
+	uint32_t found;
+	uint64_t missing;
+	uint32_t first;          /* OK and found > 0: its slot in the emitted list */
+	uint32_t reserved;       /* 0 */
+} vc_bam_piece_status;
+typedef struct {
+	uint64_t records;        /* regular records of OK pieces: counted */
+	uint64_t bases;
+	uint64_t irregular_off;  /* UINT64_MAX without one */
+	uint32_t found;          /* records emitted, the irregular ones among them */
+	uint32_t irregular;
+	uint32_t n_short, n_cut, n_noroom;   /* pieces */
+	uint32_t n_pieces;
+} vc_bam_pieces_res;
+int vc_bam_scan_pieces_device(vc_bam *b, const uint8_t *d_text, size_t text_bytes, const vc_bam_piece *d_pieces,
+                              size_t n_pieces, void *stream);
+int vc_bam_scan_pieces_block(vc_bam *b, const uint8_t *text, size_t text_bytes, const vc_bam_piece *pieces, size_t n_pieces);
+int vc_bam_pieces_result(vc_bam *b, vc_bam_pieces_res *res, vc_bam_piece_status *status, size_t n_status, uint32_t *offs,
+                         size_t n_offs);
+
 /* count_bam_variants (bam-vaf-counter.c:417-470) for one file: its own stderr
  * lines, the regions and weights of items 5 and 6 from this file's header and
  * index, every record through the kernels.  n_threads inflate BGZF blocks.
@@ -798,9 +885,53 @@ int vc_bam_text_kernel_ms(vc_bam *b, float *find_ms, float *check_ms);
  * it.  $VAFC_BGZF = host: the host reader alone (DESIGN 16 has the
  * measurement that decided the default).  vc_bam_inflate_info: the members of the last file that were
  * inflated on the host (header members of a device pass among them) and on
- * the device (0 after a fallback). */
+ * the device (0 after a fallback).
+ *
+ * $VAFC_BAM_INDEX = seek (unset or `ignore`: nothing of this paragraph
+ * happens).  A file with an index by item 6 and with regions is read by item
+ * 9's plan when its BAI is usable for seeking: per span the members from beg
+ * >> 16 through the one at end >> 16 are read with a seek, the spans of a batch
+ * ($VAFC_BATCH_BYTES of text, always at least one span) inflated by
+ * vc_bgzf_inflate_device back to back, batch k + 1 while batch k is walked,
+ * and each span walked as one piece by vc_bam_scan_pieces_device from beg's to
+ * end's place in the text.  A piece that ends cut is read once more on its own
+ * with as many further members as the missing bytes ask for.  The stderr
+ * lines and the counts are those of the whole-file pass; st counts the records
+ * read (seqs, bases; blocks = batches, the re-read ones among them) and
+ * vc_bam_inflate_info the members inflated (device: every member read, one
+ * read a second time counted twice; host: what the host reader, which opens
+ * the file for its header and reads ahead on its threads, had inflated when
+ * the pass began, so at least the header's and a number that may differ from
+ * run to run).  On any
+ * doubt the counts are put back and the file is read as without the variable:
+ * a compressed offset of the plan that is outside the file or where no whole
+ * BGZF member starts, an offset in the text at or past (end: past) its
+ * member's ISIZE, a member that does not inflate, a piece that ends short or
+ * cut for the second time (the end of the file cuts it every time), an
+ * irregular record, or a batch of 2^32 - 16 bytes of text or more.
+ * vc_bam_seek_info: the last file's state, one of VC_BAM_SEEK_*, the spans
+ * planned, the members read (those of a second reading counted again) and the
+ * pieces read again. */
+enum {
+	VC_BAM_SEEK_OFF = 0,         /* not asked for */
+	VC_BAM_SEEK_DONE = 1,        /* the file was read by its index */
+	VC_BAM_SEEK_NO_INDEX = 2,    /* no index, one with a wrong magic, or one not usable for seeking (item 9) */
+	VC_BAM_SEEK_NO_REGIONS = 3,
+	VC_BAM_SEEK_OFFSET = 4,      /* fallbacks from here on */
+	VC_BAM_SEEK_INFLATE = 5,
+	VC_BAM_SEEK_SHORT = 6,
+	VC_BAM_SEEK_IRREGULAR = 7,
+	VC_BAM_SEEK_CUT = 8,
+	VC_BAM_SEEK_LONG = 9
+};
+typedef struct {
+	uint64_t spans, members, rereads;
+	uint32_t state;
+	uint32_t reserved;       /* 0 */
+} vc_bam_seek_res;
 int vc_bam_count_file(vc_bam *b, const char *path, int n_threads, vc_file_stats *st);
 int vc_bam_inflate_info(const vc_bam *b, uint64_t *host_members, uint64_t *device_members);
+int vc_bam_seek_info(const vc_bam *b, vc_bam_seek_res *res);
 
 /* ------------------------------------------------------------------ */
 /* vcf-vaf-counter: genotypes of a VCF as .vaf counts                  */

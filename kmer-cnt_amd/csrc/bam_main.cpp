@@ -108,9 +108,17 @@ int main(int argc, char *argv[])
 		if (getenv("VAFC_PHASES") && rc == VC_OK) {
 			uint64_t hm = 0, dm = 0;
 			(void)vc_bam_inflate_info(bam, &hm, &dm);
-			fprintf(stderr, "[P::main] %s: inflate host %llu device %llu members, %llu records, %llu bases, %.4f s\n", fn,
+			vc_bam_seek_res sk;
+			memset(&sk, 0, sizeof sk);
+			(void)vc_bam_seek_info(bam, &sk);
+			fprintf(stderr, "[P::main] %s: inflate host %llu device %llu members, %llu records, %llu bases, %.4f s", fn,
 			        (unsigned long long)hm, (unsigned long long)dm, (unsigned long long)fst.seqs,
 			        (unsigned long long)fst.bases, fst.seconds);
+			// $VAFC_BAM_INDEX=seek: the state (VC_BAM_SEEK_*), the plan's spans, the members read, the pieces read again
+			if (sk.state != VC_BAM_SEEK_OFF)
+				fprintf(stderr, ", seek state %u spans %llu members %llu rereads %llu", sk.state, (unsigned long long)sk.spans,
+				        (unsigned long long)sk.members, (unsigned long long)sk.rereads);
+			fprintf(stderr, "\n");
 		}
 		if (rc != VC_OK && rc != VC_EIO && rc != VC_EINVAL) {
 			fprintf(stderr, "Error: counting failed on %s (%s)\n", fn, vc_strerror(rc));

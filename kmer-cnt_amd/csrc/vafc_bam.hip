@@ -375,6 +375,79 @@ __global__ void __launch_bounds__(BAM_BLOCK) bam_text_check_kernel(VcBamTextArgs
 	}
 }
 
+struct VcBamPieceArgs {
+	const uint8_t *text;
+	uint64_t len;
+	const vc_bam_piece *pieces;   // [n_pieces]
+	uint32_t n_pieces;
+	uint32_t max_recs;            // room in offs
+	vc_bam_piece_status *out;     // [n_pieces]
+	uint32_t *offs;
+	VbtResult *res;
+};
+
+const int BAM_PIECE_BLOCK = 64;
+
+// n slots of the record list, never past its room: true and *at, the first.
+__device__ inline bool bam_reserve(uint32_t *n_found, uint32_t n, uint32_t room, uint32_t *at)
+{
+	uint32_t seen = atomicAdd(n_found, 0u);
+	for (;;) {
+		if ((uint64_t)seen + n > room) return false;
+		const uint32_t was = atomicCAS(n_found, seen, seen + n);
+		if (was == seen) break;
+		seen = was;
+	}
+	*at = seen;
+	return true;
+}
+
+// One lane per piece, one wave per block: the walk of vbt_piece_walk to count,
+// slots for the pieces that ended OK, and the same walk again into them.  The
+// wave sums its lanes' counts and lane 0 reserves for all of them with one
+// atomic (never past max_recs, so every slot below n_found is written); only
+// a wave whose sum finds no room (the caller's pieces overlap) lets each lane
+// try for itself.  A wave's lanes take as many trips as its longest piece; a
+// wave per piece would leave 63 lanes idle on a chain that only one lane can
+// follow.
+__global__ void __launch_bounds__(BAM_PIECE_BLOCK) bam_piece_walk_kernel(VcBamPieceArgs P)
+{
+	const int lane = threadIdx.x;
+	const uint64_t i = (uint64_t)blockIdx.x * BAM_PIECE_BLOCK + threadIdx.x;
+	const bool live = i < P.n_pieces;
+	vc_bam_piece p = {0, 0, 0};
+	vc_bam_piece_status s;
+	s.status = VC_BAM_PIECE_OK;
+	s.found = s.first = s.reserved = 0;
+	s.missing = 0;
+	if (live) {
+		p = P.pieces[i];
+		s.status = vbt_piece_walk(P.text, P.len, p, &s.found, &s.missing, nullptr, 0);
+	}
+	const uint32_t want = s.status == VC_BAM_PIECE_OK ? s.found : 0;
+	const uint64_t upto = bam_wave_scan(want, lane);
+	const uint64_t total = __shfl((unsigned long long)upto, 63, 64);
+	uint32_t base = 0;
+	int fits = 0;
+	if (lane == 0 && total && total <= P.max_recs) fits = bam_reserve(&P.res->n_found, (uint32_t)total, P.max_recs, &base) ? 1 : 0;
+	fits = __shfl(fits, 0, 64);
+	base = __shfl(base, 0, 64);
+	if (want) {
+		uint32_t at = base + (uint32_t)(upto - want);
+		if (!fits && !bam_reserve(&P.res->n_found, want, P.max_recs, &at)) s.status = VC_BAM_PIECE_NOROOM;
+		if (s.status == VC_BAM_PIECE_OK) {
+			uint32_t again;
+			uint64_t none;
+			s.first = at;
+			(void)vbt_piece_walk(P.text, P.len, p, &again, &none, P.offs + at, s.found);
+		}
+	}
+	if (s.status == VC_BAM_PIECE_SHORT) atomicAdd(&P.res->n_short, 1u);
+	else if (s.status == VC_BAM_PIECE_CUT) atomicAdd(&P.res->n_cut, 1u);
+	else if (s.status == VC_BAM_PIECE_NOROOM) atomicAdd(&P.res->n_noroom, 1u);
+	if (live) P.out[i] = s;
+}
+
 } // namespace
 
 namespace {
@@ -521,6 +594,54 @@ int scan_text(vc_bam *c, const uint8_t *d_text, size_t text_bytes, uint64_t entr
 	HIPCK(hipGetLastError());
 	HIPCK(c->text_timer.end(st));
 	HIPCK(c->check_timer.begin(st));
+	hipLaunchKernelGGL(bam_text_check_kernel, dim3(rgrid), dim3(BAM_BLOCK), 0, st, T);
+	HIPCK(hipGetLastError());
+	HIPCK(c->check_timer.end(st));
+	return launch(c, c->d_trecs, max_recs, d_text, text_bytes, st, &c->d_tres.p->n_found);
+}
+
+// The piece walk, the check of what it emitted and the two count kernels
+// behind them, on st; d_pieces is read by the walk, so it stays until st has
+// passed it.
+int scan_pieces(vc_bam *c, const uint8_t *d_text, size_t text_bytes, const vc_bam_piece *d_pieces, size_t n_pieces, hipStream_t st)
+{
+	if (text_bytes > 0xFFFFFFF0ull || n_pieces > 0x7FFFFFFFull) return VC_EINVAL;
+	const size_t max_recs = text_bytes / VBT_FIXED + 1;
+	if (n_pieces > c->d_pstat.cap) HIPCK(c->d_pstat.grow(n_pieces + n_pieces / 4 + 64));
+	if (max_recs > c->d_offs.cap) HIPCK(c->d_offs.grow(max_recs + max_recs / 4 + 1024, c->d_trecs, max_recs + max_recs / 4 + 1024));
+	c->n_pieces_last = n_pieces;
+	HIPCK(c->d_tres.zero_async(st));
+	HIPCK(hipMemsetAsync(&c->d_tres.p->irr_off, 0xFF, sizeof(uint64_t), st));   // VBT_NONE
+	if (n_pieces == 0) {
+		c->text_timer.clear();
+		c->check_timer.clear();
+		return VC_OK;
+	}
+	VcBamPieceArgs P;
+	P.text = d_text;
+	P.len = text_bytes;
+	P.pieces = d_pieces;
+	P.n_pieces = (uint32_t)n_pieces;
+	P.max_recs = (uint32_t)max_recs;
+	P.out = c->d_pstat;
+	P.offs = c->d_offs;
+	P.res = c->d_tres;
+	VcBamTextArgs T;
+	memset(&T, 0, sizeof T);
+	T.text = d_text;
+	T.len = text_bytes;
+	T.n_ref = c->n_ref;
+	T.max_recs = (uint32_t)max_recs;
+	T.offs = c->d_offs;
+	T.recs = c->d_trecs;
+	T.res = c->d_tres;
+	HIPCK(c->text_timer.begin(st));
+	const unsigned pgrid = (unsigned)((n_pieces + BAM_PIECE_BLOCK - 1) / BAM_PIECE_BLOCK);
+	hipLaunchKernelGGL(bam_piece_walk_kernel, dim3(pgrid), dim3(BAM_PIECE_BLOCK), 0, st, P);
+	HIPCK(hipGetLastError());
+	HIPCK(c->text_timer.end(st));
+	HIPCK(c->check_timer.begin(st));
+	const unsigned rgrid = (unsigned)((max_recs + BAM_BLOCK - 1) / BAM_BLOCK);
 	hipLaunchKernelGGL(bam_text_check_kernel, dim3(rgrid), dim3(BAM_BLOCK), 0, st, T);
 	HIPCK(hipGetLastError());
 	HIPCK(c->check_timer.end(st));
@@ -692,6 +813,62 @@ int vc_bam_scan_text_cuts(vc_bam *c, const uint8_t *d_text, size_t text_bytes, u
 	// pageable source: the copy has left the caller's buffer on return
 	if (n_cuts) HIPCK(hipMemcpyAsync(c->d_cuts, cuts, n_cuts * sizeof(uint64_t), hipMemcpyHostToDevice, c->st));
 	return scan_text(c, d_text, text_bytes, entry, c->d_cuts, n_cuts, final, c->st);
+}
+
+extern "C" int vc_bam_scan_pieces_device(vc_bam *c, const uint8_t *d_text, size_t text_bytes, const vc_bam_piece *d_pieces,
+                                         size_t n_pieces, void *stream)
+{
+	if (!c || (text_bytes && !d_text) || (n_pieces && !d_pieces) || ((uintptr_t)d_pieces & 7)) return VC_EINVAL;
+	HIPCK(hipSetDevice(c->dev));
+	return c->on_stream(stream, [&](hipStream_t st) { return scan_pieces(c, d_text, text_bytes, d_pieces, n_pieces, st); });
+}
+
+extern "C" int vc_bam_scan_pieces_block(vc_bam *c, const uint8_t *text, size_t text_bytes, const vc_bam_piece *pieces,
+                                        size_t n_pieces)
+{
+	if (!c || (text_bytes && !text) || (n_pieces && !pieces) || n_pieces > 0x7FFFFFFFull) return VC_EINVAL;
+	HIPCK(hipSetDevice(c->dev));
+	// the text first, the pieces behind it on an 8-byte boundary
+	const size_t at = (text_bytes + 7) & ~(size_t)7, total = at + n_pieces * sizeof(vc_bam_piece) + 8;
+	VcSlot *s;
+	const int rc = c->stage.acquire_for(total, 1, &s);
+	if (rc != VC_OK) return rc;
+	if (text_bytes) memcpy(s->h_seq, text, text_bytes);
+	if (n_pieces) memcpy(s->h_seq + at, pieces, n_pieces * sizeof(vc_bam_piece));
+	return c->stage.submit(total, 1, c->st, [&](const VcSlot &sl) {
+		return scan_pieces(c, sl.d_seq, text_bytes, reinterpret_cast<const vc_bam_piece *>(sl.d_seq + at), n_pieces, c->st);
+	}, false);
+}
+
+int vc_bam_scan_pieces_host(vc_bam *c, const uint8_t *d_text, size_t text_bytes, const vc_bam_piece *pieces, size_t n_pieces)
+{
+	if (n_pieces > c->d_pieces.cap) HIPCK(c->d_pieces.grow(n_pieces + n_pieces / 4 + 64));
+	// pageable source: the copy has left the caller's buffer on return
+	if (n_pieces) HIPCK(hipMemcpyAsync(c->d_pieces, pieces, n_pieces * sizeof(vc_bam_piece), hipMemcpyHostToDevice, c->st));
+	return scan_pieces(c, d_text, text_bytes, c->d_pieces, n_pieces, c->st);
+}
+
+extern "C" int vc_bam_pieces_result(vc_bam *c, vc_bam_pieces_res *res, vc_bam_piece_status *status, size_t n_status,
+                                    uint32_t *offs, size_t n_offs)
+{
+	if (!c || !res || (n_status && !status) || (n_offs && !offs)) return VC_EINVAL;
+	HIPCK(hipSetDevice(c->dev));
+	HIPCK(hipStreamSynchronize(c->st));
+	VbtResult r;
+	HIPCK(hipMemcpy(&r, c->d_tres, sizeof r, hipMemcpyDeviceToHost));
+	res->records = r.records;
+	res->bases = r.bases;
+	res->irregular_off = r.irr_off;
+	res->found = r.n_found;
+	res->irregular = r.irr_n;
+	res->n_short = r.n_short;
+	res->n_cut = r.n_cut;
+	res->n_noroom = r.n_noroom;
+	res->n_pieces = (uint32_t)c->n_pieces_last;
+	const size_t ns = std::min(n_status, c->n_pieces_last), no = std::min<size_t>(n_offs, r.n_found);
+	if (ns) HIPCK(hipMemcpy(status, c->d_pstat, ns * sizeof(vc_bam_piece_status), hipMemcpyDeviceToHost));
+	if (no) HIPCK(hipMemcpy(offs, c->d_offs, no * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	return VC_OK;
 }
 
 extern "C" int vc_bam_text_result(vc_bam *c, vc_bam_text_res *res)

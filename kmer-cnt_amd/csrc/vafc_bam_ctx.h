@@ -30,18 +30,26 @@ struct vc_bam : VcDevice {
 	VcDevBuf<uint32_t> d_offs;
 	VcDevBuf<vc_bam_rec> d_trecs;
 	VcDevBuf<VbtResult> d_tres;             // 1
-	VcTimer text_timer, check_timer;        // of the last scan: guess, link and emit; check
+	VcTimer text_timer, check_timer;        // of the last scan: guess, link and emit (or the piece walk); check
+	// pieces in text (vc_bam_scan_pieces_*): the outcomes of the last scan's pieces
+	VcDevBuf<vc_bam_piece_status> d_pstat;
+	VcDevBuf<vc_bam_piece> d_pieces;        // of a scan whose pieces come from the host
+	size_t n_pieces_last = 0;
 	// the device pass of vc_bam_count_file: inflater, two text buffers with
 	// room in front of the text for the tail of the piece before
 	vc_bgzf *zf = nullptr;
 	VcDevBuf<uint8_t> ztext[2];
 	size_t zhead[2] = {0, 0};
 	uint64_t z_host_members = 0, z_device_members = 0;   // of the last file (vc_bam_inflate_info)
+	vc_bam_seek_res z_seek = {0, 0, 0, 0, 0};             // of the last file (vc_bam_seek_info)
 };
 
 // vc_bam_scan_text_device on the handle's own stream with the cuts in host
 // memory (they have left it on return).
 int vc_bam_scan_text_cuts(vc_bam *c, const uint8_t *d_text, size_t text_bytes, uint64_t entry, const uint64_t *cuts,
                           size_t n_cuts, int final);
+// vc_bam_scan_pieces_device on the handle's own stream with the pieces in host
+// memory (they have left it on return).
+int vc_bam_scan_pieces_host(vc_bam *c, const uint8_t *d_text, size_t text_bytes, const vc_bam_piece *pieces, size_t n_pieces);
 
 #endif

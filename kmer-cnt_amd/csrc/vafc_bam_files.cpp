@@ -14,6 +14,13 @@
 //            borders as cuts; piece k + 1 is read, copied and inflated while
 //            piece k is scanned.  Anything the scan does not take (vafc.h lists
 //            it) puts the counts back and leaves the file to the host pass.
+//   seek     ($VAFC_BAM_INDEX=seek, beside an index and with regions) the plan
+//            of vc_bam_index_plan: per span an fseek and its members, the spans
+//            of a batch inflated back to back into one text buffer and walked
+//            as pieces in one launch (vc_bam_scan_pieces_*), batch k + 1 read,
+//            copied and inflated while batch k is walked; a cut piece is read
+//            once more with further members.  Any doubt puts the counts back
+//            and leaves the file to the two passes above.
 //
 // Compiled as HIP (it owns device buffers); no kernel is defined here.
 #include <hip/hip_runtime.h>
@@ -242,9 +249,225 @@ int count_device_pass(vc_bam *c, const char *path, vc_file_stats &st, uint64_t *
 	return VC_OK;
 }
 
-// The device pass with the handle's counts kept: VC_OK, BAM_FALLBACK with the
-// counts as they were before the file, or an error.
-int count_device(vc_bam *c, const char *path, int32_t n_ref, vc_file_stats &st)
+// ---------------------------------------------------------------------------
+// The seeking pass ($VAFC_BAM_INDEX=seek; item 9 of the contract)
+// ---------------------------------------------------------------------------
+
+// The members of some spans, compressed, and the spans as pieces of the text
+// the members inflate to.
+struct SeekBatch {
+	std::vector<uint8_t> raw;
+	std::vector<vc_bgzf_block> desc;
+	std::vector<vc_bam_piece> pieces;
+	std::vector<size_t> span_of;   // each piece's span in the plan
+	uint64_t text_len = 0;
+	int buf = 0;
+};
+
+struct BamSeek {
+	vc_bam *c;
+	FILE *fp;
+	uint64_t fsize;
+	const vc_bam_span *spans;
+	size_t n_spans;
+	size_t cap;          // text of one batch
+	vc_file_stats &st;
+	size_t next = 0;     // span
+	uint64_t members = 0, rereads = 0;
+	uint32_t why = VC_BAM_SEEK_DONE;
+	std::vector<uint8_t> mem = std::vector<uint8_t>(VC_BGZF_MAX_MEMBER);
+	std::vector<std::pair<size_t, uint64_t>> again;   // spans whose piece was cut, and the bytes missing
+
+	int give_up(uint32_t reason)
+	{
+		why = reason;
+		return BAM_FALLBACK;
+	}
+
+	// The members of span i, from the one at beg >> 16 through the one at end >>
+	// 16 and on until `extra` more bytes of text are there, behind what b holds.
+	int read_span(SeekBatch &b, size_t i, uint64_t extra)
+	{
+		const uint64_t beg_c = spans[i].beg >> 16, end_c = spans[i].end >> 16;
+		const uint32_t beg_u = (uint32_t)(spans[i].beg & 0xFFFF), end_u = (uint32_t)(spans[i].end & 0xFFFF);
+		if (beg_c >= fsize || end_c > fsize || fseeko(fp, (off_t)beg_c, SEEK_SET) != 0) return give_up(VC_BAM_SEEK_OFFSET);
+		vc_bam_piece p;
+		p.entry = b.text_len + beg_u;
+		p.stop = 0;
+		bool first = true, have_stop = false;
+		uint64_t pos = beg_c, extra_got = 0;
+		while (!have_stop || extra_got < extra) {
+			if (!have_stop && pos > end_c) return give_up(VC_BAM_SEEK_OFFSET);   // no member starts at end >> 16
+			VcBgzfMember m;
+			const int r = vc_bgzf_read_member(fp, mem.data(), &m);
+			if (r < 0) return give_up(VC_BAM_SEEK_OFFSET);
+			if (r == 0) {
+				// the end of the file: where a span may end, with nothing behind it
+				if (!have_stop && (pos != end_c || end_u != 0 || first)) return give_up(VC_BAM_SEEK_OFFSET);
+				if (!have_stop) p.stop = b.text_len;
+				have_stop = true;
+				break;
+			}
+			if (first && beg_u >= m.isize) return give_up(VC_BAM_SEEK_OFFSET);
+			first = false;
+			if (have_stop) extra_got += m.isize;
+			if (pos == end_c) {
+				if (end_u > m.isize) return give_up(VC_BAM_SEEK_OFFSET);
+				p.stop = b.text_len + end_u;
+				have_stop = true;
+			}
+			vc_bgzf_block d;
+			d.in_off = b.raw.size() + m.payload;
+			d.in_len = (uint32_t)m.payload_len;
+			d.isize = m.isize;
+			d.out_off = b.text_len;
+			d.crc32 = m.crc32;
+			d.reserved = 0;
+			b.desc.push_back(d);
+			b.raw.insert(b.raw.end(), mem.data(), mem.data() + m.size);
+			b.text_len += m.isize;
+			pos += m.size;
+			if (b.text_len >= 0xFFFFFFF0ull) return give_up(VC_BAM_SEEK_LONG);
+		}
+		p.limit = b.text_len;
+		b.pieces.push_back(p);
+		b.span_of.push_back(i);
+		return VC_OK;
+	}
+
+	// The next spans of the plan, up to a batch's text.
+	int fill(SeekBatch &b, int buf)
+	{
+		b = SeekBatch();
+		b.buf = buf;
+		while (next < n_spans && (b.pieces.empty() || b.text_len < cap)) {
+			const int rc = read_span(b, next, 0);
+			if (rc != VC_OK) return rc;
+			++next;
+		}
+		return VC_OK;
+	}
+
+	// H2D and inflate on the inflater's stream, into the batch's text buffer.
+	int submit(SeekBatch &b)
+	{
+		const size_t desc_at = (b.raw.size() + 7) & ~(size_t)7, nb = b.desc.size();
+		const size_t total = desc_at + nb * sizeof(vc_bgzf_block);
+		VcSlot *s;
+		const int rc = c->stage.acquire_for(total + 8, 1, &s);
+		if (rc != VC_OK) return rc;
+		memcpy(s->h_seq, b.raw.data(), b.raw.size());
+		memcpy(s->h_seq + desc_at, b.desc.data(), nb * sizeof(vc_bgzf_block));
+		c->zhead[b.buf] = 0;
+		if (c->ztext[b.buf].cap < b.text_len + 1) HIPCK(c->ztext[b.buf].grow((size_t)b.text_len + 65536));
+		uint8_t *d_text = c->ztext[b.buf];
+		const size_t raw_len = b.raw.size();
+		const uint64_t tl = b.text_len;
+		return c->stage.submit(total, 1, (hipStream_t)vc_bgzf_stream(c->zf), [&](const VcSlot &sl) {
+			return vc_bgzf_inflate_device(c->zf, sl.d_seq, raw_len, reinterpret_cast<const vc_bgzf_block *>(sl.d_seq + desc_at), nb,
+			                              d_text, (size_t)tl, VC_STREAM_CTX);
+		}, false);
+	}
+
+	// Wait for the batch's text and walk, check and count its pieces.
+	int scan(SeekBatch &b)
+	{
+		size_t n = 0, ok = 0;
+		const int rc = vc_bgzf_finish(c->zf, nullptr, 0, &n, &ok);
+		if (rc != VC_OK) return rc;
+		if (ok != b.desc.size()) return give_up(VC_BAM_SEEK_INFLATE);
+		members += b.desc.size();
+		return vc_bam_scan_pieces_host(c, c->ztext[b.buf], (size_t)b.text_len, b.pieces.data(), b.pieces.size());
+	}
+
+	// What the batch's pieces came to; a cut piece of the plan's own batches is
+	// noted to be read again, one of a second reading ends the pass.
+	int result(SeekBatch &b, bool second)
+	{
+		vc_bam_pieces_res res;
+		std::vector<vc_bam_piece_status> stat(b.pieces.size());
+		const int rc = vc_bam_pieces_result(c, &res, stat.data(), stat.size(), nullptr, 0);
+		if (rc != VC_OK) return rc;
+		if (res.n_short) return give_up(VC_BAM_SEEK_SHORT);
+		if (res.irregular) return give_up(VC_BAM_SEEK_IRREGULAR);
+		if (res.n_noroom) return give_up(VC_BAM_SEEK_LONG);   // cannot be: the pieces are disjoint
+		if (res.n_cut && second) return give_up(VC_BAM_SEEK_CUT);
+		for (size_t i = 0; i < stat.size(); ++i)
+			if (stat[i].status == VC_BAM_PIECE_CUT) again.emplace_back(b.span_of[i], stat[i].missing ? stat[i].missing : 1);
+		st.seqs += res.records;
+		st.bases += res.bases;
+		++st.blocks;
+		return VC_OK;
+	}
+
+	int run()
+	{
+		SeekBatch bt[2];
+		int rc = fill(bt[0], 0);
+		if (rc == VC_OK && !bt[0].pieces.empty()) rc = submit(bt[0]);
+		for (int k = 0; rc == VC_OK && !bt[k & 1].pieces.empty(); ++k) {
+			SeekBatch &b = bt[k & 1], &nx = bt[(k + 1) & 1];
+			if ((rc = scan(b)) != VC_OK) break;
+			// the next batch is read, copied and inflated while this one is walked and counted
+			if ((rc = fill(nx, b.buf ^ 1)) != VC_OK) break;
+			if (!nx.pieces.empty() && (rc = submit(nx)) != VC_OK) break;
+			rc = result(b, false);
+		}
+		for (size_t i = 0; rc == VC_OK && i < again.size(); ++i) {
+			SeekBatch b;
+			if ((rc = read_span(b, again[i].first, again[i].second)) != VC_OK) break;
+			if ((rc = submit(b)) != VC_OK || (rc = scan(b)) != VC_OK) break;
+			rc = result(b, true);
+			++rereads;
+		}
+		return rc;
+	}
+};
+
+// The records the index's spans hold, through the device inflater and the
+// piece walk.  BAM_FALLBACK: the file is the whole-file pass's (sk.state says
+// why); the counts may have been touched.
+int count_seek_pass(vc_bam *c, const char *path, const std::vector<int32_t> &tid, const std::vector<int32_t> &start,
+                    const std::vector<int32_t> &end, vc_file_stats &st, vc_bam_seek_res &sk)
+{
+	vc_bam_span *spans = nullptr;
+	size_t n_spans = 0;
+	int rc = vc_bam_index_plan(path, nullptr, c->n_ref, tid.data(), start.data(), end.data(), tid.size(), &spans, &n_spans);
+	struct Owner {
+		vc_bam_span *spans;
+		FILE *fp;
+		~Owner()
+		{
+			vc_bam_index_plan_free(spans);
+			if (fp) fclose(fp);
+		}
+	} own{spans, nullptr};
+	if (rc != VC_OK) {
+		sk.state = VC_BAM_SEEK_NO_INDEX;
+		return rc == VC_BAM_NO_SEEK || rc == VC_EINVAL ? BAM_FALLBACK : rc;
+	}
+	sk.spans = n_spans;
+	own.fp = fopen(path, "rb");
+	if (!own.fp || fseeko(own.fp, 0, SEEK_END) != 0) {
+		sk.state = VC_BAM_SEEK_OFFSET;
+		return BAM_FALLBACK;
+	}
+	const uint64_t fsize = (uint64_t)ftello(own.fp);
+	if (!c->zf && (rc = vc_bgzf_create(&c->zf, c->dev)) != VC_OK) return rc;
+	BamSeek seek{c, own.fp, fsize, spans, n_spans, vc_batch_bytes(BAM_BATCH_BYTES), st};
+	rc = seek.run();
+	sk.members = seek.members;
+	sk.rereads = seek.rereads;
+	sk.state = seek.why;
+	return rc;
+}
+
+// The device pass (or, with regions given, the seeking pass) with the handle's
+// counts kept: VC_OK, BAM_FALLBACK with the counts as they were before the
+// file, or an error.
+int count_device(vc_bam *c, const char *path, int32_t n_ref, vc_file_stats &st, uint64_t header_members = 0,
+                 const std::vector<int32_t> *tid = nullptr, const std::vector<int32_t> *start = nullptr,
+                 const std::vector<int32_t> *end = nullptr)
 {
 	HIPCK(hipSetDevice(c->dev));
 	HIPCK(hipStreamSynchronize(c->st));
@@ -253,8 +476,14 @@ int count_device(vc_bam *c, const char *path, int32_t n_ref, vc_file_stats &st)
 	HIPCK(hipMemcpy(before.data(), c->d_counts, 2 * (size_t)c->n_pat * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	const int32_t n_ref_before = c->n_ref;
 	c->n_ref = n_ref;
-	uint64_t host_members = 0, device_members = 0;
-	int rc = count_device_pass(c, path, st, &host_members, &device_members);
+	uint64_t host_members = header_members, device_members = 0;
+	int rc;
+	if (tid) {
+		rc = count_seek_pass(c, path, *tid, *start, *end, st, c->z_seek);
+		device_members = c->z_seek.members;
+	} else {
+		rc = count_device_pass(c, path, st, &host_members, &device_members);
+	}
 	c->n_ref = n_ref_before;
 	// whatever is in flight has ended before the buffers are left alone
 	if (c->zf) (void)vc_bgzf_finish(c->zf, nullptr, 0, nullptr, nullptr);
@@ -276,6 +505,13 @@ extern "C" int vc_bam_inflate_info(const vc_bam *c, uint64_t *host_members, uint
 	if (!c) return VC_EINVAL;
 	if (host_members) *host_members = c->z_host_members;
 	if (device_members) *device_members = c->z_device_members;
+	return VC_OK;
+}
+
+extern "C" int vc_bam_seek_info(const vc_bam *c, vc_bam_seek_res *res)
+{
+	if (!c || !res) return VC_EINVAL;
+	*res = c->z_seek;
 	return VC_OK;
 }
 
@@ -323,6 +559,11 @@ extern "C" int vc_bam_count_file(vc_bam *c, const char *path, int n_threads, vc_
 		}
 	}
 	const bool weighted = have_index && have_regions;
+	const char *how = getenv("VAFC_BAM_INDEX");
+	const bool seek = how && strcmp(how, "seek") == 0 && weighted && !tid.empty();
+	memset(&c->z_seek, 0, sizeof c->z_seek);
+	if (how && strcmp(how, "seek") == 0 && !seek)
+		c->z_seek.state = !have_index ? VC_BAM_SEEK_NO_INDEX : VC_BAM_SEEK_NO_REGIONS;
 	rc = vc_bam_set_regions(c, tid.data(), start.data(), end.data(), tid.size());
 	if (rc != VC_OK) return rc;
 	if (weighted && tid.empty()) {
@@ -330,6 +571,16 @@ extern "C" int vc_bam_count_file(vc_bam *c, const char *path, int n_threads, vc_
 		st.seconds = vc_now() - t0;
 		if (stats) *stats = st;
 		return VC_OK;
+	}
+	// $VAFC_BAM_INDEX = seek: the index's spans alone, where the file can be read so
+	if (seek) {
+		rc = count_device(c, path, (int32_t)rd.refs().size(), st, rd.members(), &tid, &start, &end);
+		if (rc != BAM_FALLBACK) {
+			st.seconds = vc_now() - t0;
+			if (stats) *stats = st;
+			return rc;
+		}
+		memset(&st, 0, sizeof st);
 	}
 	// $VAFC_BGZF = host | device; unset: BAM_BGZF_DEFAULT_DEVICE
 	const char *e = getenv("VAFC_BGZF");

@@ -22,6 +22,9 @@
 //             (VBT_STOP_FIT)
 //   check     per record found: the field tests of VcBamReader::next_batch
 //             (vafc_bam.cpp); a record that fails one is irregular
+//   pieces    many short chains in one text, each with the entry an index gives
+//             (vbt_piece_walk): no guess and no link, the same walk rule, ended
+//             at the piece's stop and bounded by the piece's limit
 //
 // Bounds, by construction: every read of text is a byte load at a position
 // tested against len before it is issued; a walk over a segment of n bytes
@@ -67,6 +70,7 @@ struct VbtResult {
 	uint32_t rewalked;    // segments whose guess was not the true entry
 	uint32_t short_stop;  // the walk stopped at a block_size < 32
 	uint32_t n_found;     // records found, irregular ones included
+	uint32_t n_short, n_cut, n_noroom, pad;   // of a piece walk: pieces that ended so
 };
 
 VBT_HD uint32_t vbt_le16(const uint8_t *t, uint64_t o) { return (uint32_t)t[o] | (uint32_t)t[o + 1] << 8; }
@@ -197,6 +201,47 @@ VBT_HD void vbt_link_end(const uint8_t *t, uint64_t len, uint64_t e, uint32_t st
 		res->irr_off = e;
 		res->irr_n = 1;
 	}
+}
+
+// A piece (vc_bam_piece of include/vafc.h): a chain whose entry is known, as
+// the index gives it.  The walk takes every record that starts in [entry,
+// stop) and lies whole below limit, under the rule of vbt_walk; entry and stop
+// past limit, and limit past the text, are clamped, so that every read is at a
+// position tested against the clamped limit and a piece of n bytes behind its
+// entry takes at most n / 36 + 2 trips.  offs, when given, takes the records'
+// offsets (at most max_offs: the count of an earlier walk of the same piece).
+// *missing: the bytes of a cut record that lie past limit, 0 where its
+// block_size word is not whole either.
+VBT_HD uint32_t vbt_piece_walk(const uint8_t *t, uint64_t text_bytes, const vc_bam_piece &p, uint32_t *count, uint64_t *missing,
+                               uint32_t *offs, uint32_t max_offs)
+{
+	const uint64_t limit = p.limit < text_bytes ? p.limit : text_bytes;
+	const uint64_t stop = p.stop < limit ? p.stop : limit;
+	uint64_t o = p.entry < limit ? p.entry : limit;
+	uint32_t n = 0, status = VC_BAM_PIECE_OK;
+	*missing = 0;
+	const uint64_t trips = o < stop ? (limit - o) / VBT_FIXED + 2 : 0;
+	for (uint64_t i = 0; i < trips && o < stop; ++i) {
+		if (limit - o < 4) {
+			status = VC_BAM_PIECE_CUT;
+			break;
+		}
+		const int32_t bl = (int32_t)vbt_le32(t, o);
+		if (bl < 32) {
+			status = VC_BAM_PIECE_SHORT;
+			break;
+		}
+		if ((uint64_t)bl > limit - o - 4) {
+			status = VC_BAM_PIECE_CUT;
+			*missing = (uint64_t)bl - (limit - o - 4);
+			break;
+		}
+		if (offs && n < max_offs) offs[n] = (uint32_t)o;
+		++n;
+		o += 4 + (uint64_t)bl;
+	}
+	*count = n;
+	return status;
 }
 
 // The record at o, which the walk has found whole inside the text: true and

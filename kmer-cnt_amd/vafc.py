@@ -60,7 +60,8 @@ EXPORTS = (
     "vc_bam_create", "vc_bam_destroy", "vc_bam_set_regions", "vc_bam_count_block", "vc_bam_count_device",
     "vc_bam_finish", "vc_bam_reset", "vc_bam_set_counts", "vc_bam_set_long_threshold", "vc_bam_kernel_ms",
     "vc_bam_count_file", "vc_bam_scan_text_device", "vc_bam_scan_text_block", "vc_bam_text_result",
-    "vc_bam_text_kernel_ms", "vc_bam_inflate_info",
+    "vc_bam_text_kernel_ms", "vc_bam_inflate_info", "vc_bam_index_plan", "vc_bam_index_plan_free",
+    "vc_bam_scan_pieces_device", "vc_bam_scan_pieces_block", "vc_bam_pieces_result", "vc_bam_seek_info",
     "vc_vcf_probe", "vc_vcf_kind_name", "vc_vcf_header_parse", "vc_vcf_header_samples", "vc_vcf_header_type",
     "vc_vcf_header_free", "vc_vcf_eval_line", "vc_vcf_create", "vc_vcf_create_raw", "vc_vcf_destroy",
     "vc_vcf_scan_block", "vc_vcf_scan_device", "vc_vcf_hits", "vc_vcf_set_max_hits", "vc_vcf_set_block_bytes",
@@ -269,6 +270,13 @@ def lib():
         "vc_bam_text_result": (C.c_int, [P, P]),
         "vc_bam_text_kernel_ms": (C.c_int, [P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
         "vc_bam_inflate_info": (C.c_int, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "vc_bam_seek_info": (C.c_int, [P, P]),
+        "vc_bam_index_plan": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int32, P, P, P, C.c_size_t, C.POINTER(P),
+                                        C.POINTER(C.c_size_t)]),
+        "vc_bam_index_plan_free": (None, [P]),
+        "vc_bam_scan_pieces_device": (C.c_int, [P, P, C.c_size_t, P, C.c_size_t, P]),
+        "vc_bam_scan_pieces_block": (C.c_int, [P, P, C.c_size_t, P, C.c_size_t]),
+        "vc_bam_pieces_result": (C.c_int, [P, P, P, C.c_size_t, P, C.c_size_t]),
         "vc_vcf_probe": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
         "vc_vcf_kind_name": (C.c_char_p, [C.c_int]),
         "vc_vcf_header_parse": (C.c_int, [P, C.c_size_t, C.c_int, C.POINTER(P), C.POINTER(C.c_size_t)]),
@@ -1552,6 +1560,62 @@ def build_regions(db: PatternDB):
     return out
 
 
+BAM_NO_SEEK = 1                # VC_BAM_NO_SEEK
+
+
+def bam_index_plan(bam_fn, n_ref: int, regions, index_fn=None):
+    """Item 9's seek plan, no GPU: regions [(tid, start, end)] of the file's
+    merged regions -> [(beg, end)] virtual offsets, ascending and disjoint, by
+    the BAI index_fn (None: the index found for bam_fn).  None where there is
+    no index or it is not usable for seeking."""
+    tid = np.ascontiguousarray([r[0] for r in regions], dtype=np.int32)
+    start = np.ascontiguousarray([r[1] for r in regions], dtype=np.int32)
+    end = np.ascontiguousarray([r[2] for r in regions], dtype=np.int32)
+    sp, n = P(), C.c_size_t()
+    rc = lib().vc_bam_index_plan(bam_fn.encode() if bam_fn else None, index_fn.encode() if index_fn else None, n_ref,
+                                 _ptr(tid) if tid.size else None, _ptr(start) if tid.size else None,
+                                 _ptr(end) if tid.size else None, tid.size, C.byref(sp), C.byref(n))
+    if rc == BAM_NO_SEEK:
+        return None
+    _ck(rc, "vc_bam_index_plan(%s)" % (index_fn or bam_fn))
+    try:
+        a = np.frombuffer(C.string_at(sp, 16 * n.value), "<u8").reshape(-1, 2) if n.value else np.zeros((0, 2), "<u8")
+        return [(int(b), int(e)) for b, e in a]
+    finally:
+        lib().vc_bam_index_plan_free(sp)
+
+
+# vc_bam_piece, vc_bam_piece_status
+BAM_PIECE = np.dtype([("entry", "<u8"), ("stop", "<u8"), ("limit", "<u8")])
+BAM_PIECE_STATUS = np.dtype([("status", "<u4"), ("found", "<u4"), ("missing", "<u8"), ("first", "<u4"), ("reserved", "<u4")])
+BAM_PIECE_OK, BAM_PIECE_CUT, BAM_PIECE_SHORT, BAM_PIECE_NOROOM = 0, 1, 2, 3
+
+
+class BamPiecesResult(C.Structure):
+    """vc_bam_pieces_res: the totals of the last piece scan."""
+    _fields_ = [("records", C.c_uint64), ("bases", C.c_uint64), ("irregular_off", C.c_uint64), ("found", C.c_uint32),
+                ("irregular", C.c_uint32), ("n_short", C.c_uint32), ("n_cut", C.c_uint32), ("n_noroom", C.c_uint32),
+                ("n_pieces", C.c_uint32)]
+
+
+# VC_BAM_SEEK_*: from "offset" on the file fell back to the whole-file pass
+BAM_SEEK_STATES = ("off", "done", "no_index", "no_regions", "offset", "inflate", "short", "irregular", "cut", "long")
+
+
+class BamSeekInfo(C.Structure):
+    """vc_bam_seek_res: what $VAFC_BAM_INDEX=seek came to on the last file."""
+    _fields_ = [("spans", C.c_uint64), ("members", C.c_uint64), ("rereads", C.c_uint64), ("state", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+    @property
+    def name(self) -> str:
+        return BAM_SEEK_STATES[self.state]
+
+    @property
+    def fell_back(self) -> bool:
+        return self.state >= BAM_SEEK_STATES.index("offset")
+
+
 class BamTextResult(C.Structure):
     """vc_bam_text_res: the outcome of the last text scan."""
     _fields_ = [("consumed", C.c_uint64), ("records", C.c_uint64), ("bases", C.c_uint64),
@@ -1560,6 +1624,15 @@ class BamTextResult(C.Structure):
 
 
 BAM_NO_IRREGULAR = 0xFFFFFFFFFFFFFFFF     # BamTextResult.irregular_off without an irregular record
+
+
+def _bam_pieces(pieces) -> np.ndarray:
+    if isinstance(pieces, np.ndarray) and pieces.dtype == BAM_PIECE:
+        return np.ascontiguousarray(pieces)
+    out = np.zeros(len(pieces), BAM_PIECE)
+    for i, p in enumerate(pieces):
+        out[i] = tuple(p)
+    return out
 
 
 class BamCounter:
@@ -1663,11 +1736,47 @@ class BamCounter:
         _ck(lib().vc_bam_text_kernel_ms(self._h, C.byref(find), C.byref(check)), "vc_bam_text_kernel_ms")
         return find.value, check.value
 
+    def scan_pieces_block(self, text, pieces) -> None:
+        """Walk, check and count many record chains of one inflated BAM text
+        (host bytes) on the GPU in one launch: pieces = [(entry, stop, limit)]
+        or a BAM_PIECE array.  Asynchronous; pieces_result() reports."""
+        text = np.frombuffer(bytes(text), np.uint8) if isinstance(text, (bytes, bytearray)) else \
+            np.ascontiguousarray(text, dtype=np.uint8)
+        pieces = _bam_pieces(pieces)
+        _ck(lib().vc_bam_scan_pieces_block(self._h, _ptr(text) if text.size else None, text.size,
+                                           _ptr(pieces) if pieces.size else None, pieces.size), "vc_bam_scan_pieces_block")
+
+    def scan_pieces_device(self, text_ptr: int, text_bytes: int, pieces_ptr: int, n_pieces: int, stream: int = 0) -> None:
+        """The same for HBM-resident text and pieces (BAM_PIECE) on `stream`."""
+        _ck(lib().vc_bam_scan_pieces_device(self._h, P(text_ptr) if text_ptr else None, text_bytes,
+                                            P(pieces_ptr) if pieces_ptr else None, n_pieces,
+                                            P(stream) if stream else None), "vc_bam_scan_pieces_device")
+
+    def pieces_result(self):
+        """Waits for the handle's stream: (BamPiecesResult, BAM_PIECE_STATUS
+        array in the pieces' order, emitted record offsets) of the last piece
+        scan; a piece's own offsets are offs[first:first + found]."""
+        res = BamPiecesResult()
+        _ck(lib().vc_bam_pieces_result(self._h, C.byref(res), None, 0, None, 0), "vc_bam_pieces_result")
+        status = np.zeros(res.n_pieces, BAM_PIECE_STATUS)
+        offs = np.zeros(res.found, np.uint32)
+        _ck(lib().vc_bam_pieces_result(self._h, C.byref(res), _ptr(status) if status.size else None, status.size,
+                                       _ptr(offs) if offs.size else None, offs.size), "vc_bam_pieces_result")
+        return res, status, offs
+
     def inflate_info(self):
         """(host members, device members) of the last count_file."""
         h, d = C.c_uint64(), C.c_uint64()
         _ck(lib().vc_bam_inflate_info(self._h, C.byref(h), C.byref(d)), "vc_bam_inflate_info")
         return h.value, d.value
+
+    def seek_info(self) -> "BamSeekInfo":
+        """The last count_file under $VAFC_BAM_INDEX=seek: state (one of
+        BAM_SEEK_STATES by .name), spans planned, members read, pieces read
+        again."""
+        res = BamSeekInfo()
+        _ck(lib().vc_bam_seek_info(self._h, C.byref(res)), "vc_bam_seek_info")
+        return res
 
     def close(self):
         if getattr(self, "_h", None):
